@@ -11,10 +11,15 @@ boundary; device-resident, on a dedicated comm stream fenced by the decode event
 Whole-job images/s = N·4·K / max-over-ranks(time of K steps); ``per_rank`` reports each rank's
 step time and device time of its gather (µs).
 
-Rank 0 also measures the streaming guess scorer (BASELINE config 1/5): MiniLM-L6 embed +
-cosine for a 64-player micro-batch, p50 latency in ms (reported as ``p50_score_ms``).
+A plain run does only that: set up, ``--warmup`` steps, ``--steps`` timed steps, one JSON line.
+``--dump-outputs DIR`` also writes the images of the last timed step (``DIR/images.npy``, float32
+[batch, H, W, 3]; rank 0 of a multi-rank job adds the gathered rooms, ``gathered_images.npy``):
+prompts, seeds and weights depend only on the arguments, so two builds compare output for output.
 
-After the headline timed region (its fields unchanged), a 1-GPU run also records BASELINE
+Everything else is measured only with ``--full`` (after the timed region, headline fields
+unchanged).  The batch-1 latency (``batch1_s_per_image``).  On rank 0 the streaming guess scorer
+(BASELINE config 1/5): MiniLM-L6 embed + cosine for a 64-player micro-batch, p50 latency in ms
+(``p50_score_ms``), with its CPU baselines.  And a 1-GPU run also records BASELINE
 configs 4 and 5 (skippable): ``sdxl_fp8_s_per_image`` (SDXL-base 1024², 30 Euler steps, batch 1,
 fp8 attention; one warm-up + 2 timed generations, prompt -> host uint8, with its own ``finite``)
 and a short in-process live round (``live_images_per_s``, ``live_score_p50_ms`` /
@@ -28,7 +33,7 @@ process-group init and every blocking collective of a rank are bounded by ``--co
 ``--deadline-s``.  On a failure ONE JSON line is printed (by the launcher, or by rank 0 under
 torchrun) with ``value`` null, ``error`` and, for a collective / init failure, ``comm.error``.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 4] [--baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 4] [--baseline] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -70,6 +75,13 @@ def parse():
     p.add_argument("--comm-timeout-s", type=float, default=180.0,
                    help="bound on the process-group init and on every blocking collective of a rank")
     p.add_argument("--deadline-s", type=float, default=1500.0, help="launcher: overall deadline of the job")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline timed steps also measure the batch-1 latency, the guess scorer "
+                        "(GPU and CPU baselines) and, on 1 GPU, the live-round and SDXL fp8 extras "
+                        "(each skippable: --no-batch1, --no-score, --no-live, --no-sdxl)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the images of the last timed step (what the caller of "
+                        "the timed path receives) as float32 DIR/<name>.npy")
     p.add_argument("--oversubscribe", action="store_true",
                    help="allow --gpus N above the visible GPU count: the N ranks share the GPUs "
                         "(rank r on GPU r mod visible) over gloo with a host gather; RCCL refuses "
@@ -157,6 +169,28 @@ def scorer_bench(device) -> dict:
     return {"p50_score_ms": out["b64"]["p50_ms"], "p99_score_ms": out["b64"]["p99_ms"], "score_batch": 64,
             "score_latency": out, "score_latency_wordvec": wv, "cpu_minilm_1pair_p50_ms": round(float(np.percentile(lat, 50)), 3),
             "cpu_numpy_cosine_1pair_p50_ms": round(float(np.percentile(lat_np, 50)), 5)}
+
+
+DUMP_BUDGET_BYTES = 64 << 20        # of all the files of one --dump-outputs directory together
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """Write ``arrays`` (name -> tensor) as float32 ``path/<name>.npy``.  The files share
+    ``DUMP_BUDGET_BYTES``: an array above its share is stored as a fixed sample of its flattened
+    elements (sorted indices drawn without replacement from ``default_rng(0)``, so two builds
+    store the same elements).  -> name -> stored shape."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays)) // 4           # float32 elements per file
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().astype(np.float32)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def _visible_gpus() -> int:
@@ -472,6 +506,7 @@ def run_rank(args, wd: "Watchdog") -> int:
     from cassmantle_amd.utils.tracing import TRACER
     TRACER.flush()
     TRACER.reset()                      # stage means over the timed generations only
+    img = None
     t0 = time.perf_counter()
     for k in range(args.steps):
         img = one_step(args.warmup + k)
@@ -506,10 +541,19 @@ def run_rank(args, wd: "Watchdog") -> int:
         per_rank = [{"rank": i, "ms_per_step": round(float(v[0]), 2), "gather_us": round(float(v[1]), 1)}
                     for i, v in enumerate(allv)]
     wd.disarm()
+    # what the last timed step handed its caller: this rank's room and, on rank 0 of a multi-rank
+    # job, the gathered rooms of every rank (both complete: the device was synchronised above)
+    dumped = None
+    if args.dump_outputs and rank == 0 and img is not None:
+        arrays = {"images": img}
+        if gather_buf is not None:
+            arrays["gathered_images"] = torch.stack([g.cpu() for g in gather_buf])
+        dumped = dump_outputs(args.dump_outputs, arrays)
+    # everything below is measured only with --full: a plain run ends with the headline record
     # batch-1 latency: one room's single image end to end (prompt -> uint8 on host), what a
     # serving room waits on; one warm-up generation (graph capture for batch 1), then 2 timed
     b1 = None
-    if not args.no_batch1 and device.type == "cuda":
+    if args.full and not args.no_batch1 and device.type == "cuda":
         p1 = room_prompts(10_000)[:1]
         sd.generate(p1, negative, [7], steps=args.denoise_steps, scheduler=args.scheduler)
         lat1 = []
@@ -520,13 +564,13 @@ def run_rank(args, wd: "Watchdog") -> int:
         b1 = round(float(np.median(lat1)), 4)
 
     score = {}
-    if rank == 0 and not args.no_score:
+    if args.full and rank == 0 and not args.no_score:
         score = scorer_bench(device)    # noqa: F841 - reported below
 
     # BASELINE configs 5 and 4 as extras of a 1-GPU record, after every headline measurement
     extras = {}
     use_graphs, overlap = bool(sd.use_graphs), sd.decode_stream is not None
-    if world == 1 and device.type == "cuda" and args.model == "sd15" and not args.baseline:
+    if args.full and world == 1 and device.type == "cuda" and args.model == "sd15" and not args.baseline:
         if not args.no_live:
             extras.update(live_extra(args, sd, device, room_prompts, negative))
         if not args.no_sdxl:
@@ -563,9 +607,12 @@ def run_rank(args, wd: "Watchdog") -> int:
             "batch1_s_per_image": b1,       # one room, one image, prompt -> host uint8
             "stage_overlap": overlap,
             "stage_mean_ms": stage_ms,      # device time per timed generation
+            "full": bool(args.full),
             **score,
             **extras,
         }
+        if dumped is not None:
+            out["dumped"] = {"dir": args.dump_outputs, "dtype": "float32", "shapes": dumped}
         if per_rank is not None:
             out["per_rank"] = per_rank
             out["comm"] = {"backend": dist.get_backend(), "world_size": world,

@@ -39,6 +39,49 @@ def test_bench_gpus2_spawns_two_ranks():
     assert abs(out["value"] - 8 / (out["ms_per_step"] / 1e3)) / out["value"] < 0.01
 
 
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run measures the headline only (no scorer / batch-1 / extras: those need ``--full``);
+    ``--dump-outputs`` writes the last timed step's images as float32, identical from run to run."""
+    import numpy as np
+    arrs = []
+    for d in ("a", "b"):
+        r = _run(["--gpus", "1", "--model", "tiny", "--steps", "2", "--warmup", "1",
+                  "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1, r.stdout
+        out = lines[0]
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["full"] is False
+        assert abs(out["value"] - 4 / (out["ms_per_step"] / 1e3)) / out["value"] < 0.01
+        for k in ("p50_score_ms", "cpu_minilm_1pair_p50_ms", "sdxl_fp8_s_per_image", "live_images_per_s"):
+            assert k not in out
+        assert out["batch1_s_per_image"] is None
+        assert sorted(os.listdir(tmp_path / d)) == ["images.npy"]
+        a = np.load(tmp_path / d / "images.npy")
+        assert a.dtype == np.float32 and a.shape == (4, 16, 16, 3) and out["dumped"]["shapes"]["images"] == [4, 16, 16, 3]
+        assert a.min() >= 0 and a.max() <= 255 and np.array_equal(a, np.round(a))
+        arrs.append(a)
+    assert np.array_equal(arrs[0], arrs[1])
+
+
+def test_dump_outputs_samples_above_the_size_budget(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 4 * 100)       # 100 float32 per file
+    big = torch.arange(1000, dtype=torch.float32).reshape(10, 100)
+    small = torch.arange(12, dtype=torch.uint8).reshape(3, 4)
+    shapes = bench.dump_outputs(str(tmp_path), {"big": big, "small": small})
+    assert shapes == {"big": [100], "small": [3, 4]}
+    b = np.load(tmp_path / "big.npy")
+    assert b.dtype == np.float32 and len(set(b.tolist())) == 100 and np.all(np.diff(b) > 0)
+    bench.dump_outputs(str(tmp_path / "again"), {"big": big, "small": small})
+    assert np.array_equal(b, np.load(tmp_path / "again" / "big.npy"))       # the same sample every time
+    s = np.load(tmp_path / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.numpy())
+
+
 def test_bench_world_size_mismatch_fails():
     r = _run(["--gpus", "2", "--model", "tiny", "--steps", "1", "--warmup", "0", "--no-score"],
              env_extra={"WORLD_SIZE": "1", "RANK": "0"}, timeout=120)

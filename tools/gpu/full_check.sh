@@ -10,8 +10,8 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -3 gpurun_out/${tag}_tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${tag}_smoke.log 2>&1 || { tail -20 gpurun_out/${tag}_smoke.log; exit 1; }
 tail -1 gpurun_out/${tag}_smoke.log
-timeout -k 10 300 python bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err || { tail -20 gpurun_out/${tag}_bench.err; exit 1; }
-cat gpurun_out/${tag}_bench.json
+# (--full: the record with the batch-1, scorer, live-round and SDXL measurements; the JSON line goes to stdout)
+timeout -k 10 600 python bench.py --full 2> "$TMPDIR/${tag}_bench.err" || { tail -20 "$TMPDIR/${tag}_bench.err"; exit 1; }
 [ "${SKIP_PROF:-0}" = 1 ] && exit 0
 bash tools/gpu/profile.sh ${tag}_sd15 sd15 10 24 || exit 1
 bash tools/gpu/profile.sh ${tag}_sdxl sdxl 4 10 --batch 1 --fp8-attention || exit 1
