@@ -121,6 +121,13 @@ class ModelConfig:
     dtype: str = "bf16"                   # bf16 (HIP kernels) | fp32 (CPU reference path only)
     device: str = "auto"                  # auto | cpu | cuda
     gpu_blur: bool = True                 # /fetch/contents blur on the GPU (HIP kernel) when present
+    # masked images (blur cache) JPEG-encoded on the GPU (ops.jpeg_encode, HIP) instead of a
+    # device-to-host copy of the pixels + PIL per bucket; needs gpu_blur.  Off: today's bytes
+    gpu_jpeg: bool = False
+    # MCUs per restart interval, the unit of parallel entropy coding; 0 = one MCU row (W / 16).
+    # Shorter intervals code faster but every marker and DC reset costs bytes on these small
+    # blurred images (tools/bench_jpeg.py sweep: +16 % / +21 % at 4 MCUs for 512^2 / 1024^2)
+    jpeg_restart_mcus: int = 0
     use_graphs: bool = True               # hipGraph-captured denoise loop
     fp8_attention: bool = False           # BASELINE config 4 (SDXL)
     weights_path: Optional[str] = None    # diffusers-layout dir (unet/ vae/ text_encoder[_2]/ *.safetensors)

@@ -14,7 +14,7 @@ import io
 import math
 import threading
 from collections import OrderedDict
-from typing import Callable, Optional, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 from PIL import Image, ImageFilter
@@ -56,14 +56,18 @@ def quantize_radius(radius: float, bucket: float) -> float:
 
 
 BlurFn = Callable[[np.ndarray, float], np.ndarray]
+# (image, radii > 0, quality) -> one JPEG per radius, blurred and encoded on the GPU
+# (runtime.factory.build_blur_jpeg_fn)
+BlurJpegFn = Callable[[object, Sequence[float], int], List[bytes]]
 
 
 class BlurCache:
     """LRU of blurred JPEGs keyed by (content version, radius bucket)."""
 
     def __init__(self, blur_fn: Optional[BlurFn] = None, bucket: float = 0.25,
-                 quality: int = 75, capacity: int = 256) -> None:
+                 quality: int = 75, capacity: int = 256, blur_jpeg_fn: Optional[BlurJpegFn] = None) -> None:
         self.blur_fn = blur_fn or blur_pil
+        self.blur_jpeg_fn = blur_jpeg_fn
         self.bucket = bucket
         self.quality = quality
         self.capacity = capacity
@@ -97,24 +101,48 @@ class BlurCache:
                 self.hits += 1
                 return self._lru[key]
             self.misses += 1
-            arr = self._sources.get(version)
-            if arr is None:
-                ver, arr = self._decoded
-                if ver != version:
-                    arr = decode_jpeg(jpeg)
-                    self._decoded = (version, arr)
+            arr = self._source(version, jpeg)
         with TRACER.span("blur_jpeg"):
-            out = encode_jpeg(self.blur_fn(arr, r), self.quality) if r > 0 else jpeg
-        with self._lock:
-            self._lru[key] = out
-            while len(self._lru) > self.capacity:
-                self._lru.popitem(last=False)
+            if r > 0 and self.blur_jpeg_fn is not None:
+                out = self.blur_jpeg_fn(arr, [r], self.quality)[0]
+            else:
+                out = encode_jpeg(self.blur_fn(arr, r), self.quality) if r > 0 else jpeg
+        self._store([(key, out)])
         return out
 
+    def _store(self, items) -> None:
+        with self._lock:
+            for key, out in items:
+                self._lru[key] = out
+            while len(self._lru) > self.capacity:
+                self._lru.popitem(last=False)
+
+    def _source(self, version: str, jpeg: bytes):
+        """The pixels of content ``version``: its device-resident original, else the decoded JPEG
+        (call with the lock held)."""
+        arr = self._sources.get(version)
+        if arr is None:
+            ver, arr = self._decoded
+            if ver != version:
+                arr = decode_jpeg(jpeg)
+                self._decoded = (version, arr)
+        return arr
+
     def prewarm(self, version: str, jpeg: bytes, max_blur: float) -> int:
-        """Precompute every bucket for a freshly promoted image (round boundary)."""
+        """Precompute every bucket for a freshly promoted image (round boundary).  With a
+        ``blur_jpeg_fn`` all missing buckets are blurred and encoded in ONE call."""
         n = 0
         steps = int(math.ceil(max_blur / self.bucket)) if self.bucket > 0 else 0
+        if self.blur_jpeg_fn is not None:
+            radii = [quantize_radius(i * self.bucket, self.bucket) for i in range(steps + 1)]
+            with self._lock:
+                missing = [r for r in dict.fromkeys(radii) if r > 0 and (version, r) not in self._lru]
+                arr = self._source(version, jpeg) if missing else None
+                self.misses += len(missing)
+            if missing:
+                with TRACER.span("blur_jpeg"):
+                    outs = self.blur_jpeg_fn(arr, missing, self.quality)
+                self._store([((version, r), o) for r, o in zip(missing, outs)])
         for i in range(steps + 1):
             self.get(version, jpeg, i * self.bucket)
             n += 1

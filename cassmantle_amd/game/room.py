@@ -54,7 +54,7 @@ class GameRoom:
                  image_gen: Optional[ImageGenerator] = None,
                  room_id: str = "", clock: Optional[Clock] = None,
                  rng: Optional[random.Random] = None,
-                 blur_fn=None) -> None:
+                 blur_fn=None, blur_jpeg_fn=None) -> None:
         self.cfg = cfg
         self.store = store
         self.scorer = scorer
@@ -65,7 +65,8 @@ class GameRoom:
         self.rng = rng or random.Random()
         self.seeds = load_seeds()          # src/backend.py:31-34
         self.styles = load_styles()        # src/backend.py:36-39
-        self.blur_cache = BlurCache(blur_fn=blur_fn, bucket=cfg.blur_bucket, quality=cfg.jpeg_quality)
+        self.blur_cache = BlurCache(blur_fn=blur_fn, bucket=cfg.blur_bucket, quality=cfg.jpeg_quality,
+                                    blur_jpeg_fn=blur_jpeg_fn)
         self._buffer_task: Optional[asyncio.Task] = None
         self._buffer_latched = False
         self.generation_errors = 0

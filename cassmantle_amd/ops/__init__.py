@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Optional
+from typing import List, Optional
 
 import torch
 
@@ -745,6 +745,65 @@ def gaussian_blur(img: torch.Tensor, sigma: float) -> torch.Tensor:
     out = torch.empty_like(img)
     ext().gaussian_blur(img.contiguous(), w, out)
     return out
+
+
+_JPEG_PLANS: dict = {}     # (device, H, W, quality, sampling, restart_mcus) -> (tables, header) on the device
+
+
+def _jpeg_plan(device, H: int, W: int, quality: int, sampling: str, restart_mcus: int):
+    """The encoder's constant inputs on ``device``: int32 [128 + 544] quantisation | Huffman tables
+    and the uint8 header bytes (SOI .. SOS), uploaded once per key."""
+    from . import jpeg_format as jf
+    key = (device, H, W, quality, sampling, restart_mcus)
+    plan = _JPEG_PLANS.get(key)
+    if plan is None:
+        import numpy as np
+        hdr = jf.header(H, W, quality, sampling, restart_mcus)
+        lq, cq = jf.quant_tables(quality)
+        tables = np.concatenate([np.asarray(lq + cq, dtype=np.int32), jf.huff_table()])
+        if len(_JPEG_PLANS) >= 64:
+            _JPEG_PLANS.clear()
+        plan = _JPEG_PLANS[key] = (torch.from_numpy(tables).to(device),
+                                   torch.frombuffer(bytearray(hdr), dtype=torch.uint8).to(device))
+    return plan
+
+
+def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: int = 4) -> List[bytes]:
+    """Baseline JPEG (JFIF) of uint8 ``[B, H, W, 3]`` / ``[H, W, 3]`` images (a tensor, or a
+    ``DeviceImage``): one complete JPEG byte string per image, bit for bit what
+    ``ops.reference.jpeg_encode`` writes (the contract: ops/csrc/jpeg.hip).  ``sampling`` "420" |
+    "444"; ``restart_mcus`` MCUs per restart interval, the unit of parallel entropy coding (the
+    HIP path needs >= 1; 0 = no restart markers, reference only).
+
+    HIP path, all on the current stream: transform + per-interval byte count + scans, one copy of
+    the image offsets to the host (the payload size), the write pass, one copy of the payload."""
+    t = getattr(images, "tensor", images)
+    if not isinstance(t, torch.Tensor):
+        return ref.jpeg_encode(images, quality, sampling, restart_mcus)
+    if t.dim() == 3:
+        t = t[None]
+    if t.dim() != 4 or t.shape[-1] != 3 or t.dtype != torch.uint8 or t.numel() == 0:
+        raise ValueError("jpeg_encode: uint8 [B, H, W, 3] or [H, W, 3] expected")
+    if not _use_hip(t):
+        return ref.jpeg_encode(t, quality, sampling, restart_mcus)
+    from . import jpeg_format as jf
+    quality, restart_mcus = int(quality), int(restart_mcus)
+    if restart_mcus < 1:
+        raise ValueError("jpeg_encode: the HIP encoder codes restart intervals in parallel: restart_mcus >= 1")
+    B, H, W, _ = t.shape
+    _, nb, mx, my = jf.geometry(H, W, sampling)
+    tables, header = _jpeg_plan(t.device, H, W, quality, sampling, restart_mcus)
+    t = t.contiguous()
+    nint = (mx * my + restart_mcus - 1) // restart_mcus
+    coef = torch.empty((B, mx * my, nb, 64), device=t.device, dtype=torch.int16)
+    work = torch.empty(2 * B * nint + B + 1, device=t.device, dtype=torch.int32)
+    s420 = int(sampling == "420")
+    ext().jpeg_count(t, tables, header, coef, work, s420, restart_mcus)
+    base = work[: B + 1].cpu().tolist()               # device-to-host copy 1: the image offsets
+    out = torch.empty(base[-1], device=t.device, dtype=torch.uint8)
+    ext().jpeg_write(t, tables, header, coef, work, s420, restart_mcus, out, base[-1])
+    mv = memoryview(out.cpu().numpy())                # device-to-host copy 2: the payload
+    return [bytes(mv[base[i]: base[i + 1]]) for i in range(B)]
 
 
 def vae_postprocess(x: torch.Tensor) -> torch.Tensor:

@@ -858,6 +858,60 @@ void decode_attention(const at::Tensor& q, const at::Tensor& k_cache, const at::
   launch_decode_attention(a, ns, cur_stream());
 }
 
+// Batched JPEG encode, phase 1 / 2 (ops.jpeg_encode allocates: the payload size is known only
+// after phase 1's offsets reach the host).  tables: int32 [128 + 544] = quantisation | Huffman.
+JpegArgs jpeg_args(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
+                   at::Tensor& work, int64_t s420, int64_t restart) {
+  CHECK_DEV(images); CHECK_CONTIG(images); CHECK_DEV(tables); CHECK_CONTIG(tables); CHECK_DEV(header);
+  CHECK_CONTIG(header); CHECK_DEV(coef); CHECK_CONTIG(coef); CHECK_DEV(work); CHECK_CONTIG(work);
+  TORCH_CHECK(images.scalar_type() == at::kByte && images.dim() == 4 && images.size(3) == 3 && images.numel() > 0,
+              "jpeg: images uint8 [B, H, W, 3]");
+  TORCH_CHECK(tables.scalar_type() == at::kInt && tables.numel() == 128 + 544, "jpeg: tables int32 [672]");
+  TORCH_CHECK(header.scalar_type() == at::kByte && header.numel() > 0, "jpeg: header uint8");
+  TORCH_CHECK(restart >= 1 && restart < 65536, "jpeg: the HIP encoder needs 1 <= restart_mcus <= 65535");
+  JpegArgs a;
+  a.img = images.data_ptr<uint8_t>();
+  a.B = (int)images.size(0); a.H = (int)images.size(1); a.W = (int)images.size(2);
+  TORCH_CHECK(a.H < 65536 && a.W < 65536, "jpeg: image sides must be below 65536");
+  const int mcu = s420 ? 16 : 8;
+  a.nb = s420 ? 6 : 3;
+  a.mx = (a.W + mcu - 1) / mcu; a.my = (a.H + mcu - 1) / mcu;
+  a.restart = (int)restart;
+  const long long mcus = (long long)a.mx * a.my;
+  a.nint = (int)((mcus + restart - 1) / restart);
+  a.hdr_len = (int)header.numel();
+  // 32-bit payload offsets: bound by the coder's worst case (20 + 63 * 26 bits per block, every
+  // byte stuffed, one padding byte and one marker per interval)
+  TORCH_CHECK((double)a.B * ((double)a.hdr_len + (double)mcus * a.nb * 416 + (double)a.nint * 3) < 2147483648.0,
+              "jpeg: batch too large for 32-bit payload offsets");
+  TORCH_CHECK(coef.scalar_type() == at::kShort && coef.numel() == (long long)a.B * mcus * a.nb * 64,
+              "jpeg: coef int16 [B, mcus, blocks, 64]");
+  TORCH_CHECK(work.scalar_type() == at::kInt && work.numel() == 2LL * a.B * a.nint + a.B + 1,
+              "jpeg: work int32 [2 * B * intervals + B + 1]");
+  a.qtab = tables.data_ptr<int>(); a.huff = a.qtab + 128;
+  a.header = header.data_ptr<uint8_t>();
+  a.coef = coef.data_ptr<int16_t>();
+  a.base = reinterpret_cast<uint32_t*>(work.data_ptr<int>());     // [B + 1] first: what the host reads
+  a.lens = a.base + a.B + 1;
+  a.offs = a.lens + (long long)a.B * a.nint;
+  return a;
+}
+
+void jpeg_count(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
+                at::Tensor& work, int64_t s420, int64_t restart) {
+  launch_jpeg_count(jpeg_args(images, tables, header, coef, work, s420, restart), cur_stream());
+}
+
+void jpeg_write(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
+                at::Tensor& work, int64_t s420, int64_t restart, at::Tensor& out, int64_t total) {
+  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart);
+  CHECK_DEV(out); CHECK_CONTIG(out);
+  // total = base[B] as read back by the caller: every store of the write pass lands below it
+  TORCH_CHECK(out.scalar_type() == at::kByte && total > 0 && out.numel() == total, "jpeg: out uint8 [base[B]]");
+  a.out = out.data_ptr<uint8_t>();
+  launch_jpeg_write(a, cur_stream());
+}
+
 }  // namespace
 
 using nogil = py::call_guard<py::gil_scoped_release>;
@@ -903,6 +957,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("mean_pool_l2", &mean_pool_l2, nogil());
   m.def("gaussian_blur", &gaussian_blur, nogil());
   m.def("to_uint8", &to_uint8, nogil());
+  m.def("jpeg_count", &jpeg_count, nogil());
+  m.def("jpeg_write", &jpeg_write, nogil());
   m.def("timestep_embedding", &timestep_embedding, nogil());
   m.def("gather_add", &gather_add, nogil());
   m.def("concat2", &concat2, nogil());

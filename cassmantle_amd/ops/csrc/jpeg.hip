@@ -1,0 +1,331 @@
+// Batched baseline JPEG (JFIF) encoder for gfx950: uint8 [B][H][W][3] images in HBM -> one
+// complete JPEG byte string per image in one payload buffer.  ops/jpeg_format.py is the pure
+// numpy reference of the same contract and owns the tables (quantisation, Huffman, header bytes),
+// which arrive here as small device arrays.
+//
+// THE BYTE CONTRACT (integer arithmetic end to end; `>>` is an arithmetic shift = floor division)
+//
+//   Geometry.  Sampling "420": MCU = 16x16 pixels = blocks Y00 Y01 Y10 Y11 Cb Cr (6); "444":
+//   MCU = 8x8 pixels = blocks Y Cb Cr (3).  MCUs in raster order; pixel (y, x) outside the image
+//   reads (min(y, H-1), min(x, W-1)).
+//
+//   Colour (16-bit fixed point, JFIF / BT.601 full range), per pixel:
+//     Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+//     Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+//     Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+//   Chroma 2x2 mean (420):  c = (c00 + c01 + c10 + c11 + 2) >> 2, after the conversion.
+//   Level shift: s = sample - 128.
+//
+//   DCT, separable, matrix C[k][n] = round(2^13 * c(k)/2 * cos((2n+1) k pi / 16)) (DCTM below;
+//   its 8 distinct magnitudes are 2896 4017 3784 3406 2896 2276 1567 799):
+//     rows:     t[r][k] = (sum_n C[k][n] * s[r][n] + 2^8)  >> 9     (4 fraction bits kept)
+//     columns:  f[k][c] = (sum_n C[k][n] * t[n][c] + 2^13) >> 14    (8 x the DCT coefficient)
+//   Quantisation by Q (natural order, luma table for Y blocks, chroma for Cb / Cr), round half
+//   away from zero:  v = sign(f) * ((|f| + 4 Q) / (8 Q));  AC values are clamped to +-1023 (the
+//   baseline Huffman tables have no AC category 11).  Coefficients are stored in zig-zag order.
+//
+//   Entropy coding.  A restart interval is `restart` consecutive MCUs (the last may be short):
+//   DC predictors of the three components start at 0, blocks are coded with the standard
+//   category / run-length symbols (ZRL for runs of 16 zeros, EOB when the block ends in zeros),
+//   code word and value bits MSB first, every 0xFF byte followed by a stuffed 0x00, the last
+//   byte padded with 1-bits.  Interval i of an image is followed by RST(i & 7), the last one by
+//   EOI.  Intervals are therefore independent, byte-aligned units of work.
+//
+// Kernels: transform (one wave per MCU) -> count (one lane per interval runs the coder without
+// storing) -> exclusive scan per image and over the batch -> write (the same coder, storing at
+// the final offsets) + header copy.  Device memory beyond coefficients and payload is two
+// 32-bit words per interval.
+#include "common.h"
+#include "kernels.h"
+
+namespace {
+
+__constant__ const int DCTM[8][8] = {
+  { 2896,  2896,  2896,  2896,  2896,  2896,  2896,  2896},
+  { 4017,  3406,  2276,   799,  -799, -2276, -3406, -4017},
+  { 3784,  1567, -1567, -3784, -3784, -1567,  1567,  3784},
+  { 3406,  -799, -4017, -2276,  2276,  4017,   799, -3406},
+  { 2896, -2896, -2896,  2896,  2896, -2896, -2896,  2896},
+  { 2276, -4017,   799,  3406, -3406,  -799,  4017, -2276},
+  { 1567, -3784,  3784, -1567, -1567,  3784, -3784,  1567},
+  {  799, -2276,  3406, -4017,  4017, -3406,  2276,  -799},
+};
+// zig-zag position of natural (row-major) coefficient index
+__constant__ const unsigned char ZPOS[64] = {
+   0,  1,  5,  6, 14, 15, 27, 28,  2,  4,  7, 13, 16, 26, 29, 42,
+   3,  8, 12, 17, 25, 30, 41, 43,  9, 11, 18, 24, 31, 40, 44, 53,
+  10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60,
+  21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63,
+};
+
+constexpr int HUFF_WORDS = 2 * 16 + 2 * 256;   // DC luma, DC chroma, AC luma, AC chroma
+constexpr int TR_WAVES = 4;
+
+struct Ycc { int y, cb, cr; };
+CM_DEVICE Ycc rgb_to_ycc(const uint8_t* p) {
+  const int r = p[0], g = p[1], b = p[2];
+  Ycc o;
+  o.y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
+  o.cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
+  o.cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+  return o;
+}
+
+// ---------------------------------------------------------------------------------- transform
+// One wave per MCU, TR_WAVES MCUs per block.  The wave converts its MCU into level-shifted
+// 8x8 sample blocks in LDS, then lane l < 8*nb owns row (l & 7) of block (l >> 3) for the row
+// pass and column (l & 7) for the column pass; quantised values go back to LDS at their zig-zag
+// position and leave as packed dwords.
+template <bool S420>
+__global__ __launch_bounds__(64 * TR_WAVES) void jpeg_transform_kernel(JpegArgs a) {
+  constexpr int NB = S420 ? 6 : 3;
+  __shared__ int sm[TR_WAVES][NB * 64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int mcus = a.mx * a.my;
+  const long long g = (long long)blockIdx.x * TR_WAVES + wave;
+  const bool valid = g < (long long)a.B * mcus;
+  int* s = sm[wave];
+  if (valid) {
+    const int b = (int)(g / mcus), m = (int)(g % mcus);
+    const int y0 = (m / a.mx) * (S420 ? 16 : 8), x0 = (m % a.mx) * (S420 ? 16 : 8);
+    const uint8_t* img = a.img + (long long)b * a.H * a.W * 3;
+    if (S420) {
+      const int qy = lane >> 3, qx = lane & 7;
+      int cb = 2, cr = 2;
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        const int yy = 2 * qy + (d >> 1), xx = 2 * qx + (d & 1);
+        const int y = min(y0 + yy, a.H - 1), x = min(x0 + xx, a.W - 1);
+        const Ycc c = rgb_to_ycc(img + ((long long)y * a.W + x) * 3);
+        s[((yy >> 3) * 2 + (xx >> 3)) * 64 + (yy & 7) * 8 + (xx & 7)] = c.y - 128;
+        cb += c.cb;
+        cr += c.cr;
+      }
+      s[4 * 64 + lane] = (cb >> 2) - 128;
+      s[5 * 64 + lane] = (cr >> 2) - 128;
+    } else {
+      const int y = min(y0 + (lane >> 3), a.H - 1), x = min(x0 + (lane & 7), a.W - 1);
+      const Ycc c = rgb_to_ycc(img + ((long long)y * a.W + x) * 3);
+      s[lane] = c.y - 128;
+      s[64 + lane] = c.cb - 128;
+      s[128 + lane] = c.cr - 128;
+    }
+  }
+  __syncthreads();
+  const bool worker = valid && lane < NB * 8;
+  if (worker) {                       // rows
+    int* row = s + lane * 8;
+    int x[8], t[8];
+#pragma unroll
+    for (int n = 0; n < 8; ++n) x[n] = row[n];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      int acc = 1 << 8;
+#pragma unroll
+      for (int n = 0; n < 8; ++n) acc += DCTM[k][n] * x[n];
+      t[k] = acc >> 9;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) row[k] = t[k];
+  }
+  __syncthreads();
+  int v[8];
+  const int blk = lane >> 3, col = lane & 7;
+  if (worker) {                       // columns + quantisation
+    int x[8];
+#pragma unroll
+    for (int n = 0; n < 8; ++n) x[n] = s[blk * 64 + n * 8 + col];
+    const int* q = a.qtab + (blk < NB - 2 ? 0 : 64);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      int acc = 1 << 13;
+#pragma unroll
+      for (int n = 0; n < 8; ++n) acc += DCTM[k][n] * x[n];
+      const int f = acc >> 14;
+      const int q8 = q[k * 8 + col] << 3;
+      int mag = (abs(f) + (q8 >> 1)) / q8;
+      if (k * 8 + col != 0) mag = min(mag, 1023);
+      v[k] = f < 0 ? -mag : mag;
+    }
+  }
+  __syncthreads();
+  if (worker) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s[blk * 64 + ZPOS[k * 8 + col]] = v[k];
+  }
+  __syncthreads();
+  if (valid) {
+    uint32_t* dst = reinterpret_cast<uint32_t*>(a.coef + g * (NB * 64));
+    for (int i = lane; i < NB * 32; i += 64)
+      dst[i] = ((uint32_t)s[2 * i] & 0xffffu) | ((uint32_t)s[2 * i + 1] << 16);
+  }
+}
+
+// ---------------------------------------------------------------------------------- entropy coder
+// The count and the write pass run this one coder, so their byte counts cannot differ.
+template <bool WRITE>
+struct ByteSink {
+  uint64_t acc = 0;      // only the low `n` bits are pending
+  int n = 0;
+  uint32_t pos = 0;
+  uint8_t* out = nullptr;
+  CM_DEVICE void byte(uint32_t b) {
+    if (WRITE) out[pos] = (uint8_t)b;
+    ++pos;
+  }
+  CM_DEVICE void put(uint32_t bits, int len) {     // len <= 27, bits < 2^len
+    acc = (acc << len) | bits;
+    n += len;
+    while (n >= 8) {
+      const uint32_t b = (uint32_t)(acc >> (n - 8)) & 0xffu;
+      byte(b);
+      if (b == 0xffu) byte(0);
+      n -= 8;
+    }
+  }
+};
+
+template <bool WRITE>
+CM_DEVICE void put_ac(ByteSink<WRITE>& w, const uint32_t* ac, int& run, int val) {
+  if (val == 0) {
+    ++run;
+    return;
+  }
+  while (run >= 16) {
+    const uint32_t z = ac[0xF0];
+    w.put(z & 0xffffu, (int)(z >> 16));
+    run -= 16;
+  }
+  const int cat = 32 - __clz(abs(val));
+  const uint32_t bits = (uint32_t)(val < 0 ? val - 1 : val) & ((1u << cat) - 1u);
+  const uint32_t h = ac[(run << 4) | cat];
+  w.put(((h & 0xffffu) << cat) | bits, (int)(h >> 16) + cat);
+  run = 0;
+}
+
+// one lane per restart interval (gid = image * nint + interval)
+template <bool WRITE>
+__global__ __launch_bounds__(64) void jpeg_entropy_kernel(JpegArgs a) {
+  __shared__ uint32_t huff[HUFF_WORDS];
+  for (int i = threadIdx.x; i < HUFF_WORDS; i += 64) huff[i] = (uint32_t)a.huff[i];
+  __syncthreads();
+  const long long gid = (long long)blockIdx.x * 64 + threadIdx.x;
+  if (gid >= (long long)a.B * a.nint) return;
+  const int b = (int)(gid / a.nint), it = (int)(gid % a.nint);
+  const int mcus = a.mx * a.my;
+  const int m0 = it * a.restart, m1 = min(m0 + a.restart, mcus);
+  ByteSink<WRITE> w;
+  if (WRITE) w.out = a.out + a.base[b] + a.hdr_len + a.offs[gid];
+  const uint4* p = reinterpret_cast<const uint4*>(a.coef + ((long long)b * mcus + m0) * a.nb * 64);
+  int p0 = 0, p1 = 0, p2 = 0;
+  for (int m = m0; m < m1; ++m) {
+    for (int blk = 0; blk < a.nb; ++blk, p += 8) {
+      const int comp = blk < a.nb - 2 ? 0 : blk - (a.nb - 2) + 1;
+      const uint32_t* dc = huff + (comp == 0 ? 0 : 16);
+      const uint32_t* ac = huff + 32 + (comp == 0 ? 0 : 256);
+      int run = 0;
+#pragma unroll 1
+      for (int c = 0; c < 8; ++c) {
+        const uint4 q = p[c];
+        const uint32_t wd[4] = {q.x, q.y, q.z, q.w};
+        if (c == 0) {
+          const int v0 = (short)(wd[0] & 0xffffu);
+          const int pred = comp == 0 ? p0 : (comp == 1 ? p1 : p2);
+          const int d = v0 - pred;
+          if (comp == 0) p0 = v0; else if (comp == 1) p1 = v0; else p2 = v0;
+          const int cat = 32 - __clz(abs(d));            // 0 for d == 0
+          const uint32_t bits = (uint32_t)(d < 0 ? d - 1 : d) & ((1u << cat) - 1u);
+          const uint32_t h = dc[cat];
+          w.put(((h & 0xffffu) << cat) | bits, (int)(h >> 16) + cat);
+          put_ac(w, ac, run, (int)(short)(wd[0] >> 16));
+#pragma unroll
+          for (int j = 2; j < 8; ++j) put_ac(w, ac, run, (int)(short)((wd[j >> 1] >> (16 * (j & 1))) & 0xffffu));
+        } else if ((q.x | q.y | q.z | q.w) == 0u) {
+          run += 8;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) put_ac(w, ac, run, (int)(short)((wd[j >> 1] >> (16 * (j & 1))) & 0xffffu));
+        }
+      }
+      if (run > 0) w.put(ac[0] & 0xffffu, (int)(ac[0] >> 16));   // EOB
+    }
+  }
+  if (w.n > 0) w.put((1u << (8 - w.n)) - 1u, 8 - w.n);
+  w.byte(0xff);
+  w.byte(it + 1 < a.nint ? 0xD0u + (uint32_t)(it & 7) : 0xD9u);
+  if (!WRITE) a.lens[gid] = w.pos;
+}
+
+// ---------------------------------------------------------------------------------- scans
+CM_DEVICE uint32_t wave_inclusive_scan(uint32_t v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t y = __shfl_up(v, o, 64);
+    if (lane >= o) v += y;
+  }
+  return v;
+}
+
+// per image: offs = exclusive scan of lens; base[1 + image] = header + entropy bytes of the image
+__global__ __launch_bounds__(256) void jpeg_scan_image_kernel(JpegArgs a) {
+  __shared__ uint32_t wsum[4];
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const uint32_t* lens = a.lens + (long long)b * a.nint;
+  uint32_t* offs = a.offs + (long long)b * a.nint;
+  uint32_t running = 0;
+  for (int i0 = 0; i0 < a.nint; i0 += 256) {
+    const int i = i0 + tid;
+    const uint32_t v = i < a.nint ? lens[i] : 0u;
+    const uint32_t inc = wave_inclusive_scan(v, lane);
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    uint32_t pre = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k < wave) pre += wsum[k];
+      tot += wsum[k];
+    }
+    if (i < a.nint) offs[i] = running + pre + inc - v;
+    running += tot;
+    __syncthreads();
+  }
+  if (tid == 0) a.base[1 + b] = (uint32_t)a.hdr_len + running;
+}
+
+// over the batch, one wave: base[1 + i] (image sizes) -> inclusive scan in place, base[0] = 0
+__global__ __launch_bounds__(64) void jpeg_scan_batch_kernel(JpegArgs a) {
+  const int lane = threadIdx.x;
+  uint32_t running = 0;
+  for (int i0 = 0; i0 < a.B; i0 += 64) {
+    const int i = i0 + lane;
+    const uint32_t v = i < a.B ? a.base[1 + i] : 0u;
+    const uint32_t inc = wave_inclusive_scan(v, lane);
+    if (i < a.B) a.base[1 + i] = running + inc;
+    running += __shfl(inc, 63, 64);
+  }
+  if (lane == 0) a.base[0] = 0;
+}
+
+__global__ __launch_bounds__(256) void jpeg_header_kernel(JpegArgs a) {
+  uint8_t* dst = a.out + a.base[blockIdx.x];
+  for (int i = threadIdx.x; i < a.hdr_len; i += 256) dst[i] = a.header[i];
+}
+
+}  // namespace
+
+void launch_jpeg_count(const JpegArgs& a, hipStream_t s) {
+  const long long mcus = (long long)a.B * a.mx * a.my;
+  const unsigned tg = (unsigned)((mcus + TR_WAVES - 1) / TR_WAVES);
+  if (a.nb == 6) hipLaunchKernelGGL(jpeg_transform_kernel<true>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
+  else hipLaunchKernelGGL(jpeg_transform_kernel<false>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
+  const unsigned eg = (unsigned)(((long long)a.B * a.nint + 63) / 64);
+  hipLaunchKernelGGL(jpeg_entropy_kernel<false>, dim3(eg), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(jpeg_scan_image_kernel, dim3(a.B), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(jpeg_scan_batch_kernel, dim3(1), dim3(64), 0, s, a);
+}
+
+void launch_jpeg_write(const JpegArgs& a, hipStream_t s) {
+  const unsigned eg = (unsigned)(((long long)a.B * a.nint + 63) / 64);
+  hipLaunchKernelGGL(jpeg_entropy_kernel<true>, dim3(eg), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(jpeg_header_kernel, dim3(a.B), dim3(256), 0, s, a);
+}

@@ -210,3 +210,25 @@ void launch_zero(void* p, long long bytes, hipStream_t s);
 void launch_prefetch(const void* p, long long bytes, int blocks, void* sink, hipStream_t s);
 void launch_softmax_rows(const float* S, uint16_t* P, int rows, int cols, int Nq, int causal,
                          const int* kv_lens, hipStream_t s);
+
+// batched baseline JPEG encoder (jpeg.hip; byte contract in its header comment)
+struct JpegArgs {
+  const uint8_t* img = nullptr;      // [B][H][W][3]
+  int B = 0, H = 0, W = 0;
+  int nb = 0;                        // blocks per MCU: 6 (4:2:0, 16x16 MCU) or 3 (4:4:4, 8x8 MCU)
+  int mx = 0, my = 0;                // MCUs per row / MCU rows
+  int restart = 0, nint = 0;         // MCUs per restart interval, intervals per image
+  const int* qtab = nullptr;         // [2][64] luma, chroma quantisation tables, natural order
+  const int* huff = nullptr;         // [2*16 + 2*256] (length << 16) | code: DC luma, DC chroma, AC luma, AC chroma
+  int16_t* coef = nullptr;           // [B][mx*my][nb][64] quantised zig-zag coefficients
+  uint32_t* lens = nullptr;          // [B][nint] bytes per interval (stuffing, padding, RSTn / EOI included)
+  uint32_t* offs = nullptr;          // [B][nint] exclusive scan of lens per image
+  uint32_t* base = nullptr;          // [B + 1] byte offset of every image in the payload
+  const uint8_t* header = nullptr;   // SOI .. SOS, the same for every image of the batch
+  int hdr_len = 0;
+  uint8_t* out = nullptr;            // payload (launch_jpeg_write)
+};
+// transform + interval byte counts + scans: fills coef, lens, offs, base
+void launch_jpeg_count(const JpegArgs& a, hipStream_t s);
+// entropy-coded data at the final offsets + headers: fills out[0 .. base[B])
+void launch_jpeg_write(const JpegArgs& a, hipStream_t s);

@@ -1,0 +1,306 @@
+"""Baseline JPEG (JFIF) byte contract shared by the HIP encoder (``ops/csrc/jpeg.hip``) and its
+pure numpy reference (:func:`jpeg_encode`, exported as ``ops.reference.jpeg_encode``).
+
+Everything is integer arithmetic with defined rounding, so the kernel and this reference produce
+identical coefficients and identical bytes.  The formulas are documented once, in the header
+comment of ``jpeg.hip``; this module mirrors them line by line.  The tables (Annex K quantisation
+and Huffman tables, zig-zag order) and the header bytes live here only: the kernels receive them
+as small device tensors (``ops.jpeg_encode``), so there is one copy of each.
+"""
+from __future__ import annotations
+
+import struct
+from functools import lru_cache
+from typing import Dict, List, Sequence, Tuple
+
+import numpy as np
+
+# ----------------------------------------------------------------------------- tables (T.81 Annex K)
+_LUMA_Q = [16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55,
+           14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+           18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+           49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99]
+_CHROMA_Q = [17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99,
+             24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99] + [99] * 32
+
+_DC_LUMA = ([0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0], list(range(12)))
+_DC_CHROMA = ([0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0], list(range(12)))
+_AC_LUMA = ([0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d], [
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07,
+    0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0,
+    0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28,
+    0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49,
+    0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69,
+    0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89,
+    0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7,
+    0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5,
+    0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
+    0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8,
+    0xf9, 0xfa])
+_AC_CHROMA = ([0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77], [
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71,
+    0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0,
+    0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26,
+    0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+    0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68,
+    0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87,
+    0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5,
+    0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
+    0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8,
+    0xf9, 0xfa])
+
+
+def _zigzag() -> List[int]:
+    """Natural (row-major) index of the coefficient at each zig-zag position."""
+    order = sorted(range(64), key=lambda i: (i // 8 + i % 8,
+                                             (i // 8) if (i // 8 + i % 8) % 2 else (i % 8)))
+    return order
+
+
+ZIGZAG = _zigzag()                     # ZIGZAG[z] = natural index
+SAMPLINGS = ("420", "444")
+
+# 8-point DCT-II matrix in 13-bit fixed point: DCT_A[j] = round(8192 * cos(j*pi/16) / 2) for
+# j = 1..7, and 2896 = round(8192 / (2*sqrt(2))) for the DC row (jpeg.hip holds the same 8 numbers)
+DCT_A = (2896, 4017, 3784, 3406, 2896, 2276, 1567, 799)
+DCT_BITS = 13
+PASS1_KEEP = 4                         # fraction bits kept between the row and the column pass
+OUT_KEEP = 3                           # fraction bits of the DCT output going into the quantiser
+
+
+def dct_matrix() -> np.ndarray:
+    """C[k][n] = c(k)/2 * cos((2n+1) k pi / 16) * 2^13, folded onto DCT_A by integer symmetry."""
+    C = np.zeros((8, 8), dtype=np.int64)
+    for k in range(8):
+        for n in range(8):
+            if k == 0:
+                C[k, n] = DCT_A[0]
+                continue
+            j = ((2 * n + 1) * k) % 32
+            if j > 16:
+                j = 32 - j
+            sign = 1
+            if j > 8:
+                sign, j = -1, 16 - j
+            C[k, n] = 0 if j == 8 else sign * DCT_A[j]
+    return C
+
+
+def quant_tables(quality: int) -> Tuple[List[int], List[int]]:
+    """Annex K tables scaled by the libjpeg quality rule, natural order."""
+    q = max(1, min(100, int(quality)))
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    scale = lambda base: [max(1, min(255, (b * s + 50) // 100)) for b in base]   # noqa: E731
+    return scale(_LUMA_Q), scale(_CHROMA_Q)
+
+
+def _huff_codes(bits: Sequence[int], vals: Sequence[int]) -> Dict[int, Tuple[int, int]]:
+    """Canonical code assignment (T.81 Annex C): symbol -> (code, length)."""
+    out, code, k = {}, 0, 0
+    for length in range(1, 17):
+        for _ in range(bits[length - 1]):
+            out[vals[k]] = (code, length)
+            code += 1
+            k += 1
+        code <<= 1
+    return out
+
+
+@lru_cache(maxsize=None)
+def huff_table() -> np.ndarray:
+    """int32 [2*16 + 2*256]: ``(length << 16) | code`` per symbol for DC luma, DC chroma (16
+    slots each, 12 used), AC luma, AC chroma (256 each); 0 marks a symbol that has no code."""
+    t = np.zeros(2 * 16 + 2 * 256, dtype=np.int32)
+    for base, (bits, vals) in ((0, _DC_LUMA), (16, _DC_CHROMA), (32, _AC_LUMA), (32 + 256, _AC_CHROMA)):
+        for sym, (code, length) in _huff_codes(bits, vals).items():
+            t[base + sym] = (length << 16) | code
+    return t
+
+
+def geometry(H: int, W: int, sampling: str) -> Tuple[int, int, int, int]:
+    """(MCU edge in pixels, blocks per MCU, MCUs per row, MCU rows)."""
+    if sampling not in SAMPLINGS:
+        raise ValueError(f"sampling={sampling!r}: expected one of {SAMPLINGS}")
+    m = 16 if sampling == "420" else 8
+    return m, (6 if sampling == "420" else 3), (W + m - 1) // m, (H + m - 1) // m
+
+
+def _seg(marker: int, payload: bytes) -> bytes:
+    return struct.pack(">BBH", 0xFF, marker, len(payload) + 2) + payload
+
+
+@lru_cache(maxsize=64)
+def header(H: int, W: int, quality: int, sampling: str, restart_mcus: int) -> bytes:
+    """SOI / APP0 / DQT / SOF0 / DHT / DRI / SOS for one image (the entropy-coded data and EOI
+    follow)."""
+    if not (0 < H < 65536 and 0 < W < 65536):
+        raise ValueError("jpeg: image sides must be in 1..65535")
+    if not 0 <= restart_mcus < 65536:
+        raise ValueError("jpeg: restart_mcus must be in 0..65535")
+    geometry(H, W, sampling)
+    lq, cq = quant_tables(quality)
+    out = b"\xff\xd8"
+    out += _seg(0xE0, b"JFIF\x00\x01\x01\x00" + struct.pack(">HHBB", 1, 1, 0, 0))
+    out += _seg(0xDB, bytes([0]) + bytes(lq[i] for i in ZIGZAG) + bytes([1]) + bytes(cq[i] for i in ZIGZAG))
+    hv = 0x22 if sampling == "420" else 0x11
+    out += _seg(0xC0, struct.pack(">BHHB", 8, H, W, 3) + bytes([1, hv, 0, 2, 0x11, 1, 3, 0x11, 1]))
+    dht = b""
+    for tc_th, (bits, vals) in ((0x00, _DC_LUMA), (0x10, _AC_LUMA), (0x01, _DC_CHROMA), (0x11, _AC_CHROMA)):
+        dht += bytes([tc_th]) + bytes(bits) + bytes(vals)
+    out += _seg(0xC4, dht)
+    if restart_mcus:
+        out += _seg(0xDD, struct.pack(">H", restart_mcus))
+    out += _seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
+    return out
+
+
+# ----------------------------------------------------------------------------- transform
+def _div_floor_shift(x: np.ndarray, sh: int) -> np.ndarray:
+    return (x + (1 << (sh - 1))) >> sh        # arithmetic shift: floor((x + half) / 2^sh)
+
+
+def coefficients(img: np.ndarray, quality: int, sampling: str) -> np.ndarray:
+    """uint8 [H, W, 3] -> int16 [mcus, blocks per MCU, 64] quantised zig-zag coefficients."""
+    H, W, _ = img.shape
+    m, nb, mx, my = geometry(H, W, sampling)
+    # edge replication up to a whole MCU
+    ys = np.minimum(np.arange(my * m), H - 1)
+    xs = np.minimum(np.arange(mx * m), W - 1)
+    p = img[ys][:, xs].astype(np.int64)
+    R, G, B = p[..., 0], p[..., 1], p[..., 2]
+    Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16
+    Cb = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16
+    Cr = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16
+    if sampling == "420":
+        sub = lambda c: (c[0::2, 0::2] + c[0::2, 1::2] + c[1::2, 0::2] + c[1::2, 1::2] + 2) >> 2   # noqa: E731
+        Cb, Cr = sub(Cb), sub(Cr)
+
+    def blocks(c: np.ndarray) -> np.ndarray:       # [h, w] -> [h/8, w/8, 8, 8], level-shifted
+        h, w = c.shape
+        return (c - 128).reshape(h // 8, 8, w // 8, 8).transpose(0, 2, 1, 3)
+
+    yb, cbb, crb = blocks(Y), blocks(Cb), blocks(Cr)
+    if sampling == "420":
+        # MCU (i, j): Y blocks (2i,2j) (2i,2j+1) (2i+1,2j) (2i+1,2j+1), then Cb, Cr
+        yq = yb.reshape(my, 2, mx, 2, 8, 8).transpose(0, 2, 1, 3, 4, 5).reshape(my, mx, 4, 8, 8)
+        blk = np.concatenate([yq, cbb[:, :, None], crb[:, :, None]], axis=2)
+    else:
+        blk = np.stack([yb, cbb, crb], axis=2)
+    blk = blk.reshape(my * mx, nb, 8, 8)
+    C = dct_matrix()
+    t = _div_floor_shift(np.einsum("kn,mbrn->mbrk", C, blk), DCT_BITS - PASS1_KEEP)      # rows
+    f = _div_floor_shift(np.einsum("kn,mbnc->mbkc", C, t), DCT_BITS + PASS1_KEEP - OUT_KEEP)     # columns, x8
+    lq, cq = quant_tables(quality)
+    q = np.empty((nb, 8, 8), dtype=np.int64)
+    nluma = nb - 2
+    q[:nluma] = np.asarray(lq).reshape(8, 8)
+    q[nluma:] = np.asarray(cq).reshape(8, 8)
+    q <<= OUT_KEEP
+    v = np.sign(f) * ((np.abs(f) + (q >> 1)) // q)          # round half away from zero
+    v = v.reshape(my * mx, nb, 64)
+    v[..., 1:] = np.clip(v[..., 1:], -1023, 1023)           # baseline AC magnitude categories 1..10
+    return v[..., ZIGZAG].astype(np.int16)
+
+
+# ----------------------------------------------------------------------------- entropy coder
+class _Bits:
+    __slots__ = ("out", "acc", "n", "stuffed")
+
+    def __init__(self) -> None:
+        self.out = bytearray()
+        self.acc = 0
+        self.n = 0
+        self.stuffed = 0
+
+    def put(self, code: int, length: int) -> None:
+        self.acc = (self.acc << length) | code
+        self.n += length
+        while self.n >= 8:
+            b = (self.acc >> (self.n - 8)) & 0xFF
+            self.out.append(b)
+            if b == 0xFF:
+                self.out.append(0)
+                self.stuffed += 1
+            self.n -= 8
+        self.acc &= (1 << self.n) - 1
+
+    def flush(self) -> None:
+        if self.n:
+            self.put((1 << (8 - self.n)) - 1, 8 - self.n)      # pad with 1-bits
+
+
+def _category(v: int) -> int:
+    return abs(v).bit_length()
+
+
+def entropy(coef: np.ndarray, restart_mcus: int):
+    """int16 [mcus, nb, 64] -> (scan bytes with RSTn markers, stats)."""
+    huff = huff_table()
+    mcus, nb, _ = coef.shape
+    per = restart_mcus if restart_mcus else mcus
+    nint = (mcus + per - 1) // per
+    out = bytearray()
+    stats = {"stuffed": 0, "zrl": 0, "max_dc_cat": 0, "intervals": nint}
+    rows = coef.tolist()
+    for it in range(nint):
+        w = _Bits()
+        pred = [0, 0, 0]
+        for mcu in rows[it * per: (it + 1) * per]:
+            for b, blk in enumerate(mcu):
+                comp = 0 if b < nb - 2 else b - (nb - 2) + 1
+                dc_base, ac_base = (0, 32) if comp == 0 else (16, 32 + 256)
+                d = blk[0] - pred[comp]
+                pred[comp] = blk[0]
+                cat = _category(d)
+                stats["max_dc_cat"] = max(stats["max_dc_cat"], cat)
+                h = int(huff[dc_base + cat])
+                w.put(h & 0xFFFF, h >> 16)
+                if cat:
+                    w.put((d if d >= 0 else d - 1) & ((1 << cat) - 1), cat)
+                run = 0
+                for k in range(1, 64):
+                    v = blk[k]
+                    if v == 0:
+                        run += 1
+                        continue
+                    while run >= 16:
+                        h = int(huff[ac_base + 0xF0])
+                        w.put(h & 0xFFFF, h >> 16)
+                        stats["zrl"] += 1
+                        run -= 16
+                    cat = _category(v)
+                    h = int(huff[ac_base + (run << 4 | cat)])
+                    w.put(h & 0xFFFF, h >> 16)
+                    w.put((v if v >= 0 else v - 1) & ((1 << cat) - 1), cat)
+                    run = 0
+                if run:
+                    h = int(huff[ac_base])
+                    w.put(h & 0xFFFF, h >> 16)
+        w.flush()
+        stats["stuffed"] += w.stuffed
+        out += w.out
+        if it + 1 < nint:
+            out += bytes([0xFF, 0xD0 + (it & 7)])
+    return bytes(out), stats
+
+
+def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: int = 4,
+                return_stats: bool = False):
+    """Baseline JPEG of uint8 ``[B, H, W, 3]`` (or ``[H, W, 3]``) images: one byte string per
+    image.  ``restart_mcus`` MCUs per restart interval (0: no DRI, one interval).  With
+    ``return_stats`` also a dict per image: ``stuffed`` (0xFF bytes that needed a stuffed zero),
+    ``zrl`` (ZRL symbols), ``max_dc_cat`` (largest DC difference category), ``intervals``."""
+    arr = images.detach().cpu().numpy() if hasattr(images, "detach") else np.asarray(images)
+    if arr.ndim == 3:
+        arr = arr[None]
+    if arr.ndim != 4 or arr.shape[-1] != 3 or arr.dtype != np.uint8:
+        raise ValueError("jpeg_encode: uint8 [B, H, W, 3] or [H, W, 3] expected")
+    _, H, W, _ = arr.shape
+    hdr = header(H, W, int(quality), sampling, int(restart_mcus))
+    outs, stats = [], []
+    for img in arr:
+        scan, st = entropy(coefficients(img, int(quality), sampling), int(restart_mcus))
+        outs.append(hdr + scan + b"\xff\xd9")
+        stats.append(st)
+    return (outs, stats) if return_stats else outs

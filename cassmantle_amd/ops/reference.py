@@ -19,6 +19,8 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
+from .jpeg_format import jpeg_encode  # noqa: F401  (baseline JPEG: the contract of ops/csrc/jpeg.hip)
+
 
 def _act(y: torch.Tensor, act: Optional[str]) -> torch.Tensor:
     if act is None or act == "none":

@@ -11,7 +11,7 @@ from __future__ import annotations
 import contextlib
 import os
 
-from typing import Callable, Optional
+from typing import Callable, Optional, Sequence
 
 import numpy as np
 import torch
@@ -101,6 +101,32 @@ def build_blur_fn(cfg: Config, device: Optional[str] = None):
     return blur
 
 
+def build_blur_jpeg_fn(cfg: Config, device: Optional[str] = None):
+    """Blur + JPEG of a whole set of radii on the GPU (``gpu_jpeg``): ``fn(img, radii, quality)
+    -> [bytes]``.  Each radius is blurred by ops.gaussian_blur into one ``[len(radii), H, W, 3]``
+    buffer, which one ops.jpeg_encode call encodes: the entropy-coded bytes cross to the host,
+    not the pixels.  Everything runs on the calling thread's current stream (see build_blur_fn).
+    ``None`` unless ``gpu_jpeg`` and ``gpu_blur`` are set and the device is a GPU."""
+    dev = device or ("cuda" if torch.cuda.is_available() else "cpu")
+    if not (cfg.model.gpu_jpeg and cfg.model.gpu_blur) or not str(dev).startswith("cuda"):
+        return None
+    from .. import ops
+
+    def blur_jpeg(img, radii: Sequence[float], quality: int):
+        t = getattr(img, "tensor", None)        # DeviceImage: already in this GPU's HBM
+        if t is not None and t.device.type == "cuda":
+            x = t.to(dev, non_blocking=False)
+        else:
+            x = torch.from_numpy(np.ascontiguousarray(np.asarray(img))).to(dev, non_blocking=False)
+        x = x.contiguous()
+        buf = torch.empty((len(radii), *x.shape), device=x.device, dtype=torch.uint8)
+        for i, r in enumerate(radii):
+            ops.copy_(buf[i], ops.gaussian_blur(x, float(r)))
+        restart = cfg.model.jpeg_restart_mcus or (x.shape[1] + 15) // 16      # 0: one MCU row
+        return ops.jpeg_encode(buf, quality=quality, restart_mcus=restart)
+    return blur_jpeg
+
+
 def build_prompt_generator(cfg: Config, device: Optional[str] = None):
     """synthetic (default, template grammar) | lm (local causal LM, models/lm.py) | remote
     (HF text-generation endpoint, reference parity).  ``None`` -> per-room synthetic."""
@@ -157,4 +183,6 @@ def build_service(cfg: Config, image_gen_for_room: Optional[Callable[[str], Imag
         kw["prompt_gen"] = build_prompt_generator(cfg)
     if "blur_fn" not in kw:
         kw["blur_fn"] = build_blur_fn(cfg)
+    if "blur_jpeg_fn" not in kw:
+        kw["blur_jpeg_fn"] = build_blur_jpeg_fn(cfg)
     return GameService(cfg, scorer, image_gen_for_room=image_gen_for_room, **kw)

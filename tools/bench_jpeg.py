@@ -1,0 +1,167 @@
+"""One blur-cache prewarm (61 buckets: max_blur 15, blur_bucket 0.25) of a device-resident image,
+the parent's path against ``gpu_jpeg``:
+
+* parent: per bucket a HIP blur, the uint8 image copied to the host, PIL ``save(format="JPEG")``;
+* gpu_jpeg: 60 HIP blurs into one buffer, one ``ops.jpeg_encode`` (ops/csrc/jpeg.hip), the
+  entropy-coded bytes copied to the host.
+
+Per resolution (512, 1024; the image is media/background.png resized): the two paths interleaved
+``--reps`` times after a warm-up of each, then a sweep of ``jpeg_restart_mcus``.  Each record is
+one JSON line: host wall time, front-end CPU time (``time.process_time``), bytes moved device to
+host (counted from shapes / output sizes), and for the new path the encode kernels' device time
+(HIP events around the two launch groups of a stand-alone encode of the same blurred batch).
+
+    python tools/bench_jpeg.py [--res 512 1024] [--reps 2] [--out profiles/jpeg_prewarm.jsonl]
+"""
+import argparse
+import io
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+MAX_BLUR, BUCKET, QUALITY = 15.0, 0.25, 75
+
+
+def source_image(res: int):
+    import numpy as np
+    from PIL import Image
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    img = Image.open(os.path.join(root, "cassmantle_amd", "media", "background.png")).convert("RGB")
+    return np.asarray(img.resize((res, res), Image.LANCZOS))
+
+
+def prewarm_once(blur_fn, blur_jpeg_fn, dimg, jpeg, tag):
+    import torch
+    from cassmantle_amd.game.imaging import BlurCache
+    cache = BlurCache(blur_fn=blur_fn, bucket=BUCKET, quality=QUALITY, blur_jpeg_fn=blur_jpeg_fn)
+    cache.set_source(tag, dimg)
+    torch.cuda.synchronize()
+    w0, c0 = time.perf_counter(), time.process_time()
+    n = cache.prewarm(tag, jpeg, MAX_BLUR)
+    wall, cpu = time.perf_counter() - w0, time.process_time() - c0
+    with cache._lock:
+        outs = {r: v for (_, r), v in cache._lru.items()}
+    return n, wall, cpu, outs
+
+
+def encode_device_ms(batch, restart: int, iters: int = 5):
+    """Device time of the two launch groups of ops.jpeg_encode on ``batch`` (HIP events; nothing
+    else is queued): (transform + count + scans, write + headers) in ms."""
+    import torch
+    from cassmantle_amd import ops
+    from cassmantle_amd.ops import jpeg_format as jf
+    from cassmantle_amd.ops._ext import ext
+    B, H, W, _ = batch.shape
+    _, nb, mx, my = jf.geometry(H, W, "420")
+    nint = -(-mx * my // restart)
+    tables, header = ops._jpeg_plan(batch.device, H, W, QUALITY, "420", restart)
+    coef = torch.empty((B, mx * my, nb, 64), device="cuda", dtype=torch.int16)
+    work = torch.empty(2 * B * nint + B + 1, device="cuda", dtype=torch.int32)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    best = [1e9, 1e9]
+    for _ in range(iters):
+        ev[0].record()
+        ext().jpeg_count(batch, tables, header, coef, work, 1, restart)
+        ev[1].record()
+        total = int(work[B].item())
+        out = torch.empty(total, device="cuda", dtype=torch.uint8)
+        torch.cuda.synchronize()
+        t0 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        ext().jpeg_write(batch, tables, header, coef, work, 1, restart, out, total)
+        ev[2].record()
+        torch.cuda.synchronize()
+        best = [min(best[0], ev[0].elapsed_time(ev[1])), min(best[1], t0.elapsed_time(ev[2]))]
+    return best
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--res", type=int, nargs="+", default=[512, 1024])
+    ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--out", default=None, help="also append the JSON records to this file")
+    a = ap.parse_args(argv)
+    import numpy as np
+    import torch
+    from PIL import Image
+    if not torch.cuda.is_available():
+        print("bench_jpeg: needs a GPU", file=sys.stderr)
+        return 2
+    from cassmantle_amd import ops
+    from cassmantle_amd.config import Config
+    from cassmantle_amd.game.content import DeviceImage
+    from cassmantle_amd.game.imaging import encode_jpeg
+    from cassmantle_amd.runtime.factory import build_blur_fn, build_blur_jpeg_fn
+    ops.set_mode("hip")
+    sink = open(a.out, "a") if a.out else None
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    for res in a.res:
+        img = source_image(res).copy()
+        jpeg = encode_jpeg(img, QUALITY)
+        dimg = DeviceImage(torch.from_numpy(img).cuda())
+        dimg.host()
+        cfg = Config()
+        blur_fn = build_blur_fn(cfg, "cuda")
+        mcu_row = (res + 15) // 16
+
+        def new_fn(restart):
+            c = Config()
+            c.model.gpu_jpeg, c.model.jpeg_restart_mcus = True, restart
+            return build_blur_jpeg_fn(c, "cuda")
+
+        def run_parent(tag):
+            n, wall, cpu, outs = prewarm_once(blur_fn, None, dimg, jpeg, tag)
+            return {"res": res, "path": "parent", "buckets": n, "wall_ms": round(wall * 1e3, 2),
+                    "cpu_ms": round(cpu * 1e3, 2), "d2h_bytes": (n - 1) * res * res * 3,
+                    "jpeg_bytes": sum(len(v) for r, v in outs.items() if r > 0)}, outs
+
+        def run_new(tag, restart):
+            n, wall, cpu, outs = prewarm_once(blur_fn, new_fn(restart), dimg, jpeg, tag)
+            size = sum(len(v) for r, v in outs.items() if r > 0)
+            return {"res": res, "path": "gpu_jpeg", "restart_mcus": restart or mcu_row, "buckets": n,
+                    "wall_ms": round(wall * 1e3, 2), "cpu_ms": round(cpu * 1e3, 2),
+                    "d2h_bytes": size + 4 * n, "jpeg_bytes": size}, outs
+
+        run_parent("warm-p")
+        _, outs = run_new("warm-n", cfg.model.jpeg_restart_mcus)
+        # what the new path serves is the parent's picture: decode one bucket of each
+        _, pouts = run_parent("check")
+        for r in (0.25, 7.5, 15.0):
+            d = np.asarray(Image.open(io.BytesIO(outs[r])).convert("RGB")).astype(np.float64)
+            p = np.asarray(Image.open(io.BytesIO(pouts[r])).convert("RGB")).astype(np.float64)
+            mse = float(np.mean((d - p) ** 2))
+            emit({"res": res, "check": "psnr_new_vs_parent_decode", "radius": r,
+                  "psnr_db": round(10 * np.log10(255.0 ** 2 / max(mse, 1e-9)), 2)})
+        for rep in range(a.reps):
+            emit(dict(run_parent(f"p{rep}")[0], rep=rep))
+            emit(dict(run_new(f"n{rep}", cfg.model.jpeg_restart_mcus)[0], rep=rep))
+        # the blurred batch once, for the kernels' device time
+        radii = [i * BUCKET for i in range(1, int(MAX_BLUR / BUCKET) + 1)]
+        batch = torch.stack([ops.gaussian_blur(dimg.tensor, r) for r in radii])
+        sizes = {}
+        for restart in (1, 2, 4, 8, 16, mcu_row):
+            run_new(f"w{restart}", restart)
+            rec, _ = run_new(f"s{restart}", restart)
+            cnt, wr = encode_device_ms(batch, restart)
+            sizes[restart] = rec["jpeg_bytes"]
+            rec.update(sweep=True, row=restart == mcu_row, count_phase_device_ms=round(cnt, 3),
+                       write_phase_device_ms=round(wr, 3))
+            emit(rec)
+        emit({"res": res, "size_overhead_vs_row": {str(k): round(v / sizes[mcu_row] - 1, 4) for k, v in sizes.items()}})
+    if sink:
+        sink.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
