@@ -128,6 +128,12 @@ class ModelConfig:
     # Shorter intervals code faster but every marker and DC reset costs bytes on these small
     # blurred images (tools/bench_jpeg.py sweep: +16 % / +21 % at 4 MCUs for 512^2 / 1024^2)
     jpeg_restart_mcus: int = 0
+    # the content JPEG itself (radius 0, the bytes the content version hashes) encoded on the GPU
+    # too, and its DECODED pixels (computed there from the same coefficients) registered as the
+    # blur source: the image never crosses to the host, and masked bytes no longer depend on
+    # whether a front-end still holds the device image or decodes the stored JPEG (the reference
+    # blurs the decoded JPEG, src/server.py:53-56).  Needs gpu_jpeg and gpu_blur
+    gpu_jpeg_content: bool = False
     use_graphs: bool = True               # hipGraph-captured denoise loop
     fp8_attention: bool = False           # BASELINE config 4 (SDXL)
     weights_path: Optional[str] = None    # diffusers-layout dir (unet/ vae/ text_encoder[_2]/ *.safetensors)
@@ -193,15 +199,21 @@ class Config:
     @classmethod
     def from_args(cls, argv: Sequence[str], base: Optional["Config"] = None) -> "Config":
         cfg = base or cls.from_env()
-        it = iter(list(argv))
-        for tok in it:
+        args = list(argv)
+        i = 0
+        while i < len(args):
+            tok = args[i]
+            i += 1
             if not tok.startswith("--"):
                 continue
             tok = tok[2:]
             if "=" in tok:
                 k, v = tok.split("=", 1)
+            elif i < len(args) and not args[i].startswith("--"):
+                k, v = tok, args[i]
+                i += 1
             else:
-                k, v = tok, next(it, "true")
+                k, v = tok, "true"      # a bare flag, also in front of another one (--gpu_jpeg --gpu_jpeg_content)
             cfg.set(k, v)
         return cfg
 

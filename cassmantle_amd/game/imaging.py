@@ -74,7 +74,9 @@ class BlurCache:
         self._lru: "OrderedDict[Tuple[str, float], bytes]" = OrderedDict()
         self._decoded: Tuple[Optional[str], Optional[np.ndarray]] = (None, None)
         # version -> device-resident source image (DeviceImage) of content generated on a GPU:
-        # the blur reads it in HBM instead of decoding the JPEG (bounded: current + next content)
+        # the blur reads it in HBM instead of decoding the JPEG (bounded: current + next content).
+        # It holds the original pixels, which differ from the decoded JPEG another process would
+        # blur, or with gpu_jpeg_content the decoded pixels themselves (GameRoom._make_content)
         self._sources: "OrderedDict[str, object]" = OrderedDict()
         self._lock = threading.Lock()
         self.hits = 0
@@ -85,7 +87,7 @@ class BlurCache:
             return len(self._lru)
 
     def set_source(self, version: str, img) -> None:
-        """Register the device-resident original of content ``version`` (see ``_sources``)."""
+        """Register the device-resident pixels of content ``version`` (see ``_sources``)."""
         with self._lock:
             self._sources[version] = img
             self._sources.move_to_end(version)

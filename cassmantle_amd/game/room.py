@@ -54,7 +54,7 @@ class GameRoom:
                  image_gen: Optional[ImageGenerator] = None,
                  room_id: str = "", clock: Optional[Clock] = None,
                  rng: Optional[random.Random] = None,
-                 blur_fn=None, blur_jpeg_fn=None) -> None:
+                 blur_fn=None, blur_jpeg_fn=None, content_jpeg_fn=None) -> None:
         self.cfg = cfg
         self.store = store
         self.scorer = scorer
@@ -67,6 +67,9 @@ class GameRoom:
         self.styles = load_styles()        # src/backend.py:36-39
         self.blur_cache = BlurCache(blur_fn=blur_fn, bucket=cfg.blur_bucket, quality=cfg.jpeg_quality,
                                     blur_jpeg_fn=blur_jpeg_fn)
+        # (DeviceImage, quality) -> (JPEG bytes, DeviceImage of their decoded pixels), both made on
+        # the GPU (runtime.factory.build_content_jpeg_fn); None: PIL on the host
+        self.content_jpeg_fn = content_jpeg_fn
         self._buffer_task: Optional[asyncio.Task] = None
         self._buffer_latched = False
         self.generation_errors = 0
@@ -151,6 +154,12 @@ class GameRoom:
             log.error("[ERROR] Image generation failed")
             return None
         pdict = await asyncio.to_thread(self._prompt_dict, prompt)
+        if self.content_jpeg_fn is not None and getattr(getattr(image, "tensor", None), "is_cuda", False):
+            # encoded in HBM; the blur source is what a decoder makes of these bytes, so a process
+            # that has only the stored JPEG serves the same masked bytes.  No host copy of the pixels
+            jpeg, decoded = await asyncio.to_thread(self.content_jpeg_fn, image, self.cfg.jpeg_quality)
+            self.blur_cache.set_source(self._version(jpeg), decoded)
+            return prompt, json.dumps(pdict), jpeg
         jpeg = await asyncio.to_thread(encode_jpeg, image, self.cfg.jpeg_quality)
         if hasattr(image, "tensor"):           # landed in HBM (DeviceImage): blur it there
             self.blur_cache.set_source(self._version(jpeg), image)

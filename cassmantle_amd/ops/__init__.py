@@ -768,24 +768,36 @@ def _jpeg_plan(device, H: int, W: int, quality: int, sampling: str, restart_mcus
     return plan
 
 
-def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: int = 4) -> List[bytes]:
+def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: int = 4,
+                return_decoded: bool = False):
     """Baseline JPEG (JFIF) of uint8 ``[B, H, W, 3]`` / ``[H, W, 3]`` images (a tensor, or a
     ``DeviceImage``): one complete JPEG byte string per image, bit for bit what
     ``ops.reference.jpeg_encode`` writes (the contract: ops/csrc/jpeg.hip).  ``sampling`` "420" |
     "444"; ``restart_mcus`` MCUs per restart interval, the unit of parallel entropy coding (the
     HIP path needs >= 1; 0 = no restart markers, reference only).
 
+    ``return_decoded``: ``(bytes per image, decoded)`` instead, ``decoded`` the uint8
+    ``[B, H, W, 3]`` pixels a libjpeg decoder (PIL) gives for those bytes, bit for bit
+    ``ops.reference.jpeg_decoded`` (the decode contract: ops/csrc/jpeg.hip): a tensor on the
+    input's device (an array for an array).
+
     HIP path, all on the current stream: transform + per-interval byte count + scans, one copy of
-    the image offsets to the host (the payload size), the write pass, one copy of the payload."""
+    the image offsets to the host (the payload size), the write pass, one copy of the payload;
+    then, for ``return_decoded``, the inverse DCT of the coefficient buffer the transform filled
+    and the colour pass (queued behind the payload copy: the pixels stay in HBM)."""
     t = getattr(images, "tensor", images)
     if not isinstance(t, torch.Tensor):
-        return ref.jpeg_encode(images, quality, sampling, restart_mcus)
+        outs = ref.jpeg_encode(images, quality, sampling, restart_mcus)
+        return (outs, ref.jpeg_decoded(images, quality, sampling)) if return_decoded else outs
     if t.dim() == 3:
         t = t[None]
     if t.dim() != 4 or t.shape[-1] != 3 or t.dtype != torch.uint8 or t.numel() == 0:
         raise ValueError("jpeg_encode: uint8 [B, H, W, 3] or [H, W, 3] expected")
     if not _use_hip(t):
-        return ref.jpeg_encode(t, quality, sampling, restart_mcus)
+        outs = ref.jpeg_encode(t, quality, sampling, restart_mcus)
+        if not return_decoded:
+            return outs
+        return outs, torch.from_numpy(ref.jpeg_decoded(t, quality, sampling)).to(t.device)
     from . import jpeg_format as jf
     quality, restart_mcus = int(quality), int(restart_mcus)
     if restart_mcus < 1:
@@ -803,7 +815,13 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
     out = torch.empty(base[-1], device=t.device, dtype=torch.uint8)
     ext().jpeg_write(t, tables, header, coef, work, s420, restart_mcus, out, base[-1])
     mv = memoryview(out.cpu().numpy())                # device-to-host copy 2: the payload
-    return [bytes(mv[base[i]: base[i + 1]]) for i in range(B)]
+    outs = [bytes(mv[base[i]: base[i + 1]]) for i in range(B)]
+    if not return_decoded:
+        return outs
+    planes = torch.empty(coef.numel(), device=t.device, dtype=torch.uint8)     # one byte per padded sample
+    decoded = torch.empty((B, H, W, 3), device=t.device, dtype=torch.uint8)
+    ext().jpeg_reconstruct(coef, tables, planes, decoded, H, W, s420)
+    return outs, decoded
 
 
 def vae_postprocess(x: torch.Tensor) -> torch.Tensor:

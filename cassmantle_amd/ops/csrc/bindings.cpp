@@ -912,6 +912,37 @@ void jpeg_write(const at::Tensor& images, const at::Tensor& tables, const at::Te
   launch_jpeg_write(a, cur_stream());
 }
 
+// The decoded pixels of the JPEG whose coefficients jpeg_count left in coef (decode contract:
+// jpeg.hip): out uint8 [B, H, W, 3]; planes = scratch of one byte per padded sample.
+void jpeg_reconstruct(const at::Tensor& coef, const at::Tensor& tables, at::Tensor& planes, at::Tensor& out,
+                      int64_t H, int64_t W, int64_t s420) {
+  CHECK_DEV(coef); CHECK_CONTIG(coef); CHECK_DEV(tables); CHECK_CONTIG(tables); CHECK_DEV(planes);
+  CHECK_CONTIG(planes); CHECK_DEV(out); CHECK_CONTIG(out);
+  TORCH_CHECK(tables.scalar_type() == at::kInt && tables.numel() == 128 + 544, "jpeg: tables int32 [672]");
+  TORCH_CHECK(H > 0 && W > 0 && H < 65536 && W < 65536, "jpeg: image sides must be in 1..65535");
+  TORCH_CHECK(out.scalar_type() == at::kByte && out.dim() == 4 && out.size(0) > 0 && out.size(1) == H &&
+              out.size(2) == W && out.size(3) == 3, "jpeg: out uint8 [B, H, W, 3]");
+  JpegArgs a;
+  a.B = (int)out.size(0); a.H = (int)H; a.W = (int)W;
+  const int mcu = s420 ? 16 : 8;
+  a.nb = s420 ? 6 : 3;
+  a.mx = (a.W + mcu - 1) / mcu; a.my = (a.H + mcu - 1) / mcu;
+  const long long mcus = (long long)a.B * a.mx * a.my;
+  TORCH_CHECK(coef.scalar_type() == at::kShort && coef.numel() == mcus * a.nb * 64,
+              "jpeg: coef int16 [B, mcus, blocks, 64]");
+  // every sample store of the idct kernel and every load of the colour kernel lands in planes
+  TORCH_CHECK(planes.scalar_type() == at::kByte && planes.numel() == mcus * a.nb * 64,
+              "jpeg: planes uint8 [B * mcus * blocks * 64]");
+  TORCH_CHECK((double)a.B * a.H * ((a.W + 3) / 4) < 256.0 * 2147483647.0, "jpeg: batch too large for one launch");
+  a.qtab = tables.data_ptr<int>();
+  a.coef = coef.data_ptr<int16_t>();
+  a.planes = planes.data_ptr<uint8_t>();
+  a.dec = out.data_ptr<uint8_t>();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.planes) % 4 == 0 && reinterpret_cast<uintptr_t>(a.dec) % 4 == 0 &&
+              reinterpret_cast<uintptr_t>(a.coef) % 4 == 0, "jpeg: buffers must be 4-byte aligned");
+  launch_jpeg_reconstruct(a, cur_stream());
+}
+
 }  // namespace
 
 using nogil = py::call_guard<py::gil_scoped_release>;
@@ -959,6 +990,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("to_uint8", &to_uint8, nogil());
   m.def("jpeg_count", &jpeg_count, nogil());
   m.def("jpeg_write", &jpeg_write, nogil());
+  m.def("jpeg_reconstruct", &jpeg_reconstruct, nogil());
   m.def("timestep_embedding", &timestep_embedding, nogil());
   m.def("gather_add", &gather_add, nogil());
   m.def("concat2", &concat2, nogil());

@@ -35,6 +35,44 @@
 // storing) -> exclusive scan per image and over the batch -> write (the same coder, storing at
 // the final offsets) + header copy.  Device memory beyond coefficients and payload is two
 // 32-bit words per interval.
+//
+// THE DECODE CONTRACT (jpeg_format.reconstruct is its numpy reference): the pixels a libjpeg
+// decoder with its defaults (ISLOW inverse DCT, fancy upsampling; PIL) returns for the bytes
+// above.  They are a function of the quantised coefficients and Q alone, so they are computed
+// from the coefficient buffer the transform filled; nothing is entropy-decoded.  Integer
+// arithmetic, 32-bit words (the dequantised values come from the DCT above of 8-bit samples;
+// the reference asserts the width), `>>` arithmetic.
+//
+//   Dequantise.  d = coefficient * Q at its natural position (luma table for Y, chroma for Cb / Cr).
+//
+//   Inverse DCT (jidctint, CONST_BITS 13, PASS1_BITS 2): the 8 columns first, then the 8 rows.
+//   One 8-point pass on i0..i7:
+//     even:  z1 = (i2 + i6) * 4433;  t2 = z1 - i6 * 15137;  t3 = z1 + i2 * 6270
+//            t0 = (i0 + i4) << 13;   t1 = (i0 - i4) << 13
+//            t10 = t0 + t3;  t13 = t0 - t3;  t11 = t1 + t2;  t12 = t1 - t2
+//     odd:   a = i7, b = i5, c = i3, d = i1
+//            z1 = a + d;  z2 = b + c;  z3 = a + c;  z4 = b + d;  z5 = (z3 + z4) * 9633
+//            a *= 2446;  b *= 16819;  c *= 25172;  d *= 12299
+//            z1 *= -7373;  z2 *= -20995;  z3 = z3 * -16069 + z5;  z4 = z4 * -3196 + z5
+//            a += z1 + z3;  b += z2 + z4;  c += z2 + z3;  d += z1 + z4
+//     out 0..7 = t10+d  t11+c  t12+b  t13+a  t13-a  t12-b  t11-c  t10-d, each (v + 2^(s-1)) >> s
+//     with s = 11 in the column pass and s = 18 in the row pass.
+//   Sample = clamp(result + 128, 0, 255).
+//
+//   Chroma (420; 444 has none).  Only the ch = ceil(H/2) x cw = ceil(W/2) real samples of a
+//   chroma plane are read, indices clamped to them.  Output row 2r takes neighbour row r-1, row
+//   2r+1 takes r+1:  s[x] = 3 c[r][x] + c[neighbour][x];  then
+//     out[2x] = (3 s[x] + s[x-1] + 8) >> 4        out[2x+1] = (3 s[x] + s[x+1] + 7) >> 4
+//   With cw <= 2 libjpeg replicates instead: out[y][x] = c[y >> 1][x >> 1].
+//
+//   Colour, cb = Cb - 128, cr = Cr - 128, each clamped to 0..255:
+//     R = Y + ((91881 cr + 32768) >> 16)
+//     G = Y + ((-22554 cb - 46802 cr + 32768) >> 16)
+//     B = Y + ((116130 cb + 32768) >> 16)
+//   The output is the H x W crop.
+//
+// Kernels: idct (one wave per MCU, the mirror of transform; uint8 samples into padded planes) ->
+// colour (upsampling crosses block and MCU borders, so it reads the planes: 4 pixels per lane).
 #include "common.h"
 #include "kernels.h"
 
@@ -311,6 +349,187 @@ __global__ __launch_bounds__(256) void jpeg_header_kernel(JpegArgs a) {
   for (int i = threadIdx.x; i < a.hdr_len; i += 256) dst[i] = a.header[i];
 }
 
+// ---------------------------------------------------------------------------------- reconstruct
+// natural (row-major) coefficient index of zig-zag position (the inverse of ZPOS)
+__constant__ const unsigned char ZNAT[64] = {
+   0,  1,  8, 16,  9,  2,  3, 10, 17, 24, 32, 25, 18, 11,  4,  5,
+  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13,  6,  7, 14, 21, 28,
+  35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
+  58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63,
+};
+
+// one 8-point pass of the inverse DCT of the decode contract, in place; S = its descale shift
+template <int S>
+CM_DEVICE void idct_pass(int (&x)[8]) {
+  int z1 = (x[2] + x[6]) * 4433;
+  const int t2 = z1 - x[6] * 15137, t3 = z1 + x[2] * 6270;
+  const int t0 = (x[0] + x[4]) * 8192, t1 = (x[0] - x[4]) * 8192;
+  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  int a = x[7], b = x[5], c = x[3], d = x[1];
+  z1 = a + d;
+  int z2 = b + c, z3 = a + c, z4 = b + d;
+  const int z5 = (z3 + z4) * 9633;
+  a *= 2446; b *= 16819; c *= 25172; d *= 12299;
+  z1 *= -7373; z2 *= -20995;
+  z3 = z3 * -16069 + z5;
+  z4 = z4 * -3196 + z5;
+  a += z1 + z3; b += z2 + z4; c += z2 + z3; d += z1 + z4;
+  constexpr int half = 1 << (S - 1);
+  x[0] = (t10 + d + half) >> S; x[7] = (t10 - d + half) >> S;
+  x[1] = (t11 + c + half) >> S; x[6] = (t11 - c + half) >> S;
+  x[2] = (t12 + b + half) >> S; x[5] = (t12 - b + half) >> S;
+  x[3] = (t13 + a + half) >> S; x[4] = (t13 - a + half) >> S;
+}
+
+// LDS image of one MCU: sample (row r, column c) of block k at k * ID_BLK + r * ID_ROW + c.  The
+// odd row stride keeps both passes free of bank conflicts (lane = 8 k + column, then 8 k + row).
+constexpr int ID_ROW = 9, ID_BLK = 8 * ID_ROW;
+
+// One wave per MCU, TR_WAVES MCUs per block.  The wave unpacks its MCU's coefficients into LDS at
+// their natural position, dequantised; lane l < 8*nb owns column (l & 7) of block (l >> 3) for
+// the column pass and row (l & 7) for the row pass; the samples leave as packed dwords into the
+// padded planes: Y [B][yh][yw], then Cb [B][8 my][8 mx], then Cr (yh x yw = 16 my x 16 mx for
+// 420, 8 my x 8 mx for 444).
+template <bool S420>
+__global__ __launch_bounds__(64 * TR_WAVES) void jpeg_idct_kernel(JpegArgs a) {
+  constexpr int NB = S420 ? 6 : 3;
+  __shared__ int sm[TR_WAVES][NB * ID_BLK];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int mcus = a.mx * a.my;
+  const long long g = (long long)blockIdx.x * TR_WAVES + wave;
+  const bool valid = g < (long long)a.B * mcus;
+  int* s = sm[wave];
+  if (valid) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(a.coef + g * (NB * 64));
+    for (int i = lane; i < NB * 32; i += 64) {
+      const uint32_t w = src[i];
+      const int blk = i >> 5, z = (2 * i) & 63;
+      const int* q = a.qtab + (blk < NB - 2 ? 0 : 64);
+      const int n0 = ZNAT[z], n1 = ZNAT[z + 1];
+      s[blk * ID_BLK + (n0 >> 3) * ID_ROW + (n0 & 7)] = (int)(short)(w & 0xffffu) * q[n0];
+      s[blk * ID_BLK + (n1 >> 3) * ID_ROW + (n1 & 7)] = (int)(short)(w >> 16) * q[n1];
+    }
+  }
+  __syncthreads();
+  const bool worker = valid && lane < NB * 8;
+  const int blk = lane >> 3, own = lane & 7;
+  if (worker) {                       // columns
+    int* col = s + blk * ID_BLK + own;
+    int x[8];
+#pragma unroll
+    for (int n = 0; n < 8; ++n) x[n] = col[n * ID_ROW];
+    idct_pass<11>(x);
+#pragma unroll
+    for (int n = 0; n < 8; ++n) col[n * ID_ROW] = x[n];
+  }
+  __syncthreads();
+  if (worker) {                       // rows, level shift, clamp
+    int* row = s + blk * ID_BLK + own * ID_ROW;
+    int x[8];
+#pragma unroll
+    for (int n = 0; n < 8; ++n) x[n] = row[n];
+    idct_pass<18>(x);
+#pragma unroll
+    for (int n = 0; n < 8; ++n) row[n] = min(max(x[n] + 128, 0), 255);
+  }
+  __syncthreads();
+  if (valid) {
+    const int b = (int)(g / mcus), m = (int)(g % mcus);
+    const int my0 = m / a.mx, mx0 = m % a.mx;
+    const long long csz = (long long)mcus * 64;                 // bytes of one 8 my x 8 mx plane
+    const int cw = a.mx * 8;
+    if (S420) {                       // Y: 16 rows x 4 dwords
+      const int r = lane >> 2, xq = (lane & 3) * 4;
+      const int* p = s + ((r >> 3) * 2 + (xq >> 3)) * ID_BLK + (r & 7) * ID_ROW + (xq & 7);
+      uint8_t* dst = a.planes + ((long long)b * a.my * 16 + my0 * 16 + r) * (cw * 2) + mx0 * 16 + xq;
+      *reinterpret_cast<uint32_t*>(dst) = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    }
+    // 8x8 planes, 16 lanes each: Cb, Cr (420, after the Y planes) or Y, Cb, Cr (444)
+    constexpr int NP = S420 ? 2 : 3;
+    if (lane < NP * 16) {
+      const int pl = lane >> 4, r = (lane & 15) >> 1, xq = (lane & 1) * 4;
+      const int* p = s + (pl + NB - NP) * ID_BLK + r * ID_ROW + xq;
+      uint8_t* base = a.planes + (S420 ? 4 * csz * a.B : 0) + pl * csz * a.B;
+      uint8_t* dst = base + ((long long)b * a.my * 8 + my0 * 8 + r) * cw + mx0 * 8 + xq;
+      *reinterpret_cast<uint32_t*>(dst) = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    }
+  }
+}
+
+CM_DEVICE int clamp8(int v) { return min(max(v, 0), 255); }
+
+// One lane per run of 4 output pixels (x0 = 4 k): one dword of Y, the chroma samples it needs
+// (420: up to 2 rows x 4 columns per plane, indices clamped to the real samples), 12 bytes out.
+template <bool S420>
+__global__ __launch_bounds__(256) void jpeg_colour_kernel(JpegArgs a) {
+  const int xg = (a.W + 3) >> 2;
+  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (long long)a.B * a.H * xg) return;
+  const int x0 = (int)(gid % xg) * 4;
+  const long long line = gid / xg;                   // b * H + y
+  const int y = (int)(line % a.H), b = (int)(line / a.H);
+  const int cwp = a.mx * 8, chp = a.my * 8;          // padded 8 my x 8 mx plane
+  const int yw = S420 ? cwp * 2 : cwp, yh = S420 ? chp * 2 : chp;
+  const uint8_t* cbp = a.planes + (long long)a.B * yh * yw + (long long)b * chp * cwp;
+  const uint8_t* crp = cbp + (long long)a.B * chp * cwp;
+  const uint32_t yy = *reinterpret_cast<const uint32_t*>(a.planes + ((long long)b * yh + y) * yw + x0);
+  int cb[4], cr[4];
+  if (S420) {
+    const int ch = (a.H + 1) >> 1, cw = (a.W + 1) >> 1;
+    const int r = y >> 1, cx = x0 >> 1;
+    const uint8_t* b0 = cbp + (long long)r * cwp;
+    const uint8_t* r0 = crp + (long long)r * cwp;
+    if (cw <= 2) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = min(cx + (j >> 1), cw - 1);
+        cb[j] = b0[c];
+        cr[j] = r0[c];
+      }
+    } else {
+      const long long dn = (long long)(min(max((y & 1) ? r + 1 : r - 1, 0), ch - 1) - r) * cwp;
+      int sb[4], sr[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = min(max(cx - 1 + j, 0), cw - 1);
+        sb[j] = 3 * b0[c] + b0[dn + c];
+        sr[j] = 3 * r0[c] + r0[dn + c];
+      }
+      cb[0] = (3 * sb[1] + sb[0] + 8) >> 4; cr[0] = (3 * sr[1] + sr[0] + 8) >> 4;
+      cb[1] = (3 * sb[1] + sb[2] + 7) >> 4; cr[1] = (3 * sr[1] + sr[2] + 7) >> 4;
+      cb[2] = (3 * sb[2] + sb[1] + 8) >> 4; cr[2] = (3 * sr[2] + sr[1] + 8) >> 4;
+      cb[3] = (3 * sb[2] + sb[3] + 7) >> 4; cr[3] = (3 * sr[2] + sr[3] + 7) >> 4;
+    }
+  } else {
+    const long long o = (long long)y * cwp + x0;
+    const uint32_t wb = *reinterpret_cast<const uint32_t*>(cbp + o);
+    const uint32_t wr = *reinterpret_cast<const uint32_t*>(crp + o);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      cb[j] = (int)((wb >> (8 * j)) & 0xffu);
+      cr[j] = (int)((wr >> (8 * j)) & 0xffu);
+    }
+  }
+  uint32_t px[12];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int Y = (int)((yy >> (8 * j)) & 0xffu), u = cb[j] - 128, v = cr[j] - 128;
+    px[3 * j] = (uint32_t)clamp8(Y + ((91881 * v + 32768) >> 16));
+    px[3 * j + 1] = (uint32_t)clamp8(Y + ((-22554 * u - 46802 * v + 32768) >> 16));
+    px[3 * j + 2] = (uint32_t)clamp8(Y + ((116130 * u + 32768) >> 16));
+  }
+  uint8_t* dst = a.dec + (line * a.W + x0) * 3;
+  if ((a.W & 3) == 0) {               // rows are dword-aligned and whole: three dword stores
+    uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) d[k] = px[4 * k] | (px[4 * k + 1] << 8) | (px[4 * k + 2] << 16) | (px[4 * k + 3] << 24);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 12; ++j)
+      if (x0 + j / 3 < a.W) dst[j] = (uint8_t)px[j];
+  }
+}
+
 }  // namespace
 
 void launch_jpeg_count(const JpegArgs& a, hipStream_t s) {
@@ -328,4 +547,17 @@ void launch_jpeg_write(const JpegArgs& a, hipStream_t s) {
   const unsigned eg = (unsigned)(((long long)a.B * a.nint + 63) / 64);
   hipLaunchKernelGGL(jpeg_entropy_kernel<true>, dim3(eg), dim3(64), 0, s, a);
   hipLaunchKernelGGL(jpeg_header_kernel, dim3(a.B), dim3(256), 0, s, a);
+}
+
+void launch_jpeg_reconstruct(const JpegArgs& a, hipStream_t s) {
+  const long long mcus = (long long)a.B * a.mx * a.my;
+  const unsigned ig = (unsigned)((mcus + TR_WAVES - 1) / TR_WAVES);
+  const unsigned cg = (unsigned)(((long long)a.B * a.H * ((a.W + 3) >> 2) + 255) / 256);
+  if (a.nb == 6) {
+    hipLaunchKernelGGL(jpeg_idct_kernel<true>, dim3(ig), dim3(64 * TR_WAVES), 0, s, a);
+    hipLaunchKernelGGL(jpeg_colour_kernel<true>, dim3(cg), dim3(256), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(jpeg_idct_kernel<false>, dim3(ig), dim3(64 * TR_WAVES), 0, s, a);
+    hipLaunchKernelGGL(jpeg_colour_kernel<false>, dim3(cg), dim3(256), 0, s, a);
+  }
 }

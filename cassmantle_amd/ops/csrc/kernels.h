@@ -227,8 +227,14 @@ struct JpegArgs {
   const uint8_t* header = nullptr;   // SOI .. SOS, the same for every image of the batch
   int hdr_len = 0;
   uint8_t* out = nullptr;            // payload (launch_jpeg_write)
+  // launch_jpeg_reconstruct (decode contract in jpeg.hip's header comment)
+  uint8_t* planes = nullptr;         // scratch: Y [B][yh][yw], Cb, Cr [B][8 my][8 mx]; yh x yw = 16 my x 16 mx (4:2:0) or 8 my x 8 mx
+  uint8_t* dec = nullptr;            // [B][H][W][3] the pixels a libjpeg decoder gives for coef
 };
 // transform + interval byte counts + scans: fills coef, lens, offs, base
 void launch_jpeg_count(const JpegArgs& a, hipStream_t s);
 // entropy-coded data at the final offsets + headers: fills out[0 .. base[B])
 void launch_jpeg_write(const JpegArgs& a, hipStream_t s);
+// inverse DCT of coef into planes, then upsampling + colour into dec (reads B, H, W, nb, mx, my,
+// qtab, coef only)
+void launch_jpeg_reconstruct(const JpegArgs& a, hipStream_t s);

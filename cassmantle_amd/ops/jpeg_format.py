@@ -304,3 +304,101 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
         outs.append(hdr + scan + b"\xff\xd9")
         stats.append(st)
     return (outs, stats) if return_stats else outs
+
+
+# ----------------------------------------------------------------------------- decode contract
+# The pixels a libjpeg decoder (ISLOW inverse DCT, fancy upsampling: PIL's defaults) produces from
+# the bytes above, computed from the quantised coefficients alone.  Formulas: the DECODE CONTRACT
+# section of jpeg.hip's header comment.
+IDCT_BITS = 13                         # libjpeg jidctint CONST_BITS
+IDCT_PASS1 = 2                         # PASS1_BITS
+
+
+def _idct_pass(i, shift: int, see):
+    """One 8-point pass of the jidctint inverse DCT on the arrays i[0..7]; ``see`` is handed every
+    intermediate (the word-width check) and returns it."""
+    i0, i1, i2, i3, i4, i5, i6, i7 = i
+    z1 = see((i2 + i6) * 4433)
+    t2 = see(z1 - see(i6 * 15137))
+    t3 = see(z1 + see(i2 * 6270))
+    t0 = see((i0 + i4) << IDCT_BITS)
+    t1 = see((i0 - i4) << IDCT_BITS)
+    t10, t13, t11, t12 = see(t0 + t3), see(t0 - t3), see(t1 + t2), see(t1 - t2)
+    a, b, c, d = i7, i5, i3, i1
+    z1, z2, z3, z4 = a + d, b + c, a + c, b + d
+    z5 = see((z3 + z4) * 9633)
+    a, b, c, d = see(a * 2446), see(b * 16819), see(c * 25172), see(d * 12299)
+    z1, z2 = see(z1 * -7373), see(z2 * -20995)
+    z3, z4 = see(see(z3 * -16069) + z5), see(see(z4 * -3196) + z5)
+    a, b, c, d = see(see(a + z1) + z3), see(see(b + z2) + z4), see(see(c + z2) + z3), see(see(d + z1) + z4)
+    outs = (t10 + d, t11 + c, t12 + b, t13 + a, t13 - a, t12 - b, t11 - c, t10 - d)
+    return [see(see(v) + (1 << (shift - 1))) >> shift for v in outs]
+
+
+def _planes(samples: np.ndarray, mx: int, my: int, sampling: str):
+    """uint8-range samples [mcus, nb, 8, 8] -> padded Y, Cb, Cr planes."""
+    def plane(b: np.ndarray) -> np.ndarray:     # [my, mx, 8, 8] -> [8 my, 8 mx]
+        return b.transpose(0, 2, 1, 3).reshape(my * 8, mx * 8)
+    if sampling == "420":
+        yb = samples[:, :4].reshape(my, mx, 2, 2, 8, 8).transpose(0, 2, 4, 1, 3, 5).reshape(my * 16, mx * 16)
+        return yb, plane(samples[:, 4].reshape(my, mx, 8, 8)), plane(samples[:, 5].reshape(my, mx, 8, 8))
+    return tuple(plane(samples[:, k].reshape(my, mx, 8, 8)) for k in range(3))
+
+
+def _upsample_h2v2(c: np.ndarray, see) -> np.ndarray:
+    """[ch, cw] real chroma samples -> [2 ch, 2 cw] (libjpeg h2v2 fancy upsampling; two or fewer
+    columns are replicated, as libjpeg does there)."""
+    ch, cw = c.shape
+    y, x = np.arange(2 * ch), np.arange(2 * cw)
+    if cw <= 2:
+        return c[y >> 1][:, x >> 1]
+    near = np.clip(np.where(y & 1, (y >> 1) + 1, (y >> 1) - 1), 0, ch - 1)
+    s = 3 * c[y >> 1] + c[near]
+    side = np.clip(np.where(x & 1, (x >> 1) + 1, (x >> 1) - 1), 0, cw - 1)
+    return see(3 * s[:, x >> 1] + s[:, side] + np.where(x & 1, 7, 8)) >> 4
+
+
+def reconstruct(coef: np.ndarray, H: int, W: int, quality: int, sampling: str, stats: dict = None) -> np.ndarray:
+    """int16 [mcus, blocks per MCU, 64] quantised zig-zag coefficients (:func:`coefficients`) ->
+    uint8 [H, W, 3], the pixels a libjpeg decoder gives for the JPEG of those coefficients.
+    Computed in int64; ``stats["max_abs"]`` receives the largest magnitude of any intermediate
+    (the kernel works in 32-bit words)."""
+    _, nb, mx, my = geometry(H, W, sampling)
+    peak = [0]
+
+    def see(v):
+        peak[0] = max(peak[0], int(np.abs(v).max()))
+        return v
+
+    lq, cq = quant_tables(quality)
+    q = np.empty((nb, 64), dtype=np.int64)
+    q[:nb - 2], q[nb - 2:] = np.asarray(lq), np.asarray(cq)
+    nat = np.empty(coef.shape, dtype=np.int64)
+    nat[..., ZIGZAG] = coef
+    d = see(nat * q).reshape(-1, nb, 8, 8)
+    ws = np.stack(_idct_pass([d[..., k, :] for k in range(8)], IDCT_BITS - IDCT_PASS1, see), axis=-2)     # columns
+    px = np.stack(_idct_pass([ws[..., k] for k in range(8)], IDCT_BITS + IDCT_PASS1 + 3, see), axis=-1)   # rows
+    Y, Cb, Cr = _planes(np.clip(px + 128, 0, 255), mx, my, sampling)
+    if sampling == "420":
+        ch, cw = (H + 1) // 2, (W + 1) // 2
+        Cb, Cr = _upsample_h2v2(Cb[:ch, :cw], see), _upsample_h2v2(Cr[:ch, :cw], see)
+    Y, cb, cr = Y[:H, :W], Cb[:H, :W] - 128, Cr[:H, :W] - 128
+    R = Y + (see(91881 * cr + 32768) >> 16)
+    G = Y + (see(-22554 * cb - 46802 * cr + 32768) >> 16)
+    B = Y + (see(116130 * cb + 32768) >> 16)
+    if stats is not None:
+        stats["max_abs"] = max(stats.get("max_abs", 0), peak[0])
+    return np.clip(np.stack([R, G, B], -1), 0, 255).astype(np.uint8)
+
+
+def jpeg_decoded(images, quality: int = 75, sampling: str = "420") -> np.ndarray:
+    """uint8 ``[B, H, W, 3]`` (or ``[H, W, 3]``) images -> uint8 ``[B, H, W, 3]``: what a libjpeg
+    decoder returns for each image's :func:`jpeg_encode` bytes (any restart interval)."""
+    arr = images.detach().cpu().numpy() if hasattr(images, "detach") else np.asarray(images)
+    if arr.ndim == 3:
+        arr = arr[None]
+    if arr.ndim != 4 or arr.shape[-1] != 3 or arr.dtype != np.uint8:
+        raise ValueError("jpeg_decoded: uint8 [B, H, W, 3] or [H, W, 3] expected")
+    _, H, W, _ = arr.shape
+    return np.stack([reconstruct(coefficients(img, int(quality), sampling), H, W, int(quality), sampling)
+                     for img in arr])

@@ -19,7 +19,7 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
-from .jpeg_format import jpeg_encode  # noqa: F401  (baseline JPEG: the contract of ops/csrc/jpeg.hip)
+from .jpeg_format import jpeg_decoded, jpeg_encode  # noqa: F401  (baseline JPEG: the contracts of ops/csrc/jpeg.hip)
 
 
 def _act(y: torch.Tensor, act: Optional[str]) -> torch.Tensor:

@@ -127,6 +127,29 @@ def build_blur_jpeg_fn(cfg: Config, device: Optional[str] = None):
     return blur_jpeg
 
 
+def build_content_jpeg_fn(cfg: Config, device: Optional[str] = None):
+    """The content JPEG of a device-resident image made on the GPU (``gpu_jpeg_content``):
+    ``fn(image, quality) -> (jpeg bytes, DeviceImage of the decoded pixels)``.  One
+    ops.jpeg_encode call with ``return_decoded``: the bytes cross to the host, the pixels a
+    decoder gives for them stay in HBM and become the blur source, so a front-end that has only
+    the stored bytes (PIL decode) blurs the same pixels.  The restart rule is build_blur_jpeg_fn's;
+    everything runs on the calling thread's current stream.  ``None`` unless ``gpu_jpeg_content``,
+    ``gpu_jpeg`` and ``gpu_blur`` are set and the device is a GPU."""
+    dev = device or ("cuda" if torch.cuda.is_available() else "cpu")
+    m = cfg.model
+    if not (m.gpu_jpeg_content and m.gpu_jpeg and m.gpu_blur) or not str(dev).startswith("cuda"):
+        return None
+    from .. import ops
+    from ..game.content import DeviceImage
+
+    def content_jpeg(img, quality: int):
+        x = img.tensor.to(dev, non_blocking=False)
+        restart = m.jpeg_restart_mcus or (x.shape[1] + 15) // 16      # 0: one MCU row
+        outs, decoded = ops.jpeg_encode(x, quality=quality, restart_mcus=restart, return_decoded=True)
+        return outs[0], DeviceImage(decoded[0])
+    return content_jpeg
+
+
 def build_prompt_generator(cfg: Config, device: Optional[str] = None):
     """synthetic (default, template grammar) | lm (local causal LM, models/lm.py) | remote
     (HF text-generation endpoint, reference parity).  ``None`` -> per-room synthetic."""
@@ -185,4 +208,6 @@ def build_service(cfg: Config, image_gen_for_room: Optional[Callable[[str], Imag
         kw["blur_fn"] = build_blur_fn(cfg)
     if "blur_jpeg_fn" not in kw:
         kw["blur_jpeg_fn"] = build_blur_jpeg_fn(cfg)
+    if "content_jpeg_fn" not in kw:
+        kw["content_jpeg_fn"] = build_content_jpeg_fn(cfg)
     return GameService(cfg, scorer, image_gen_for_room=image_gen_for_room, **kw)

@@ -12,6 +12,20 @@ host (counted from shapes / output sizes), and for the new path the encode kerne
 (HIP events around the two launch groups of a stand-alone encode of the same blurred batch).
 
     python tools/bench_jpeg.py [--res 512 1024] [--reps 2] [--out profiles/jpeg_prewarm.jsonl]
+
+``--content`` measures the step before the prewarm instead, the content JPEG of one new
+device-resident image (``GameRoom._make_content``), the parent's path against ``gpu_jpeg_content``:
+
+* parent: the image copied to the host (``DeviceImage.host()``), PIL ``save(format="JPEG")``;
+* gpu_jpeg_content: one ``ops.jpeg_encode(..., return_decoded=True)``: the JPEG bytes copied to
+  the host, the decoded pixels (the blur source) left in HBM; timed to the end of its kernels.
+
+Per record: host wall time, front-end CPU time, bytes moved device to host, the JPEG's size, the
+PSNR of its decoded pixels against the original, and for the new path the device time of the idct
++ colour kernels (HIP events around a stand-alone ``jpeg_reconstruct``) and whether the device's
+decoded pixels equal PIL's decode of the bytes.
+
+    python tools/bench_jpeg.py --content [--res 512 1024] [--reps 2] [--out profiles/jpeg_content.jsonl]
 """
 import argparse
 import io
@@ -78,11 +92,108 @@ def encode_device_ms(batch, restart: int, iters: int = 5):
     return best
 
 
+def reconstruct_device_ms(t, restart: int, iters: int = 5) -> float:
+    """Device time of the idct + colour kernels behind ``return_decoded`` for the [1, H, W, 3]
+    image ``t`` (HIP events around the two launches; nothing else is queued), in ms."""
+    import torch
+    from cassmantle_amd import ops
+    from cassmantle_amd.ops import jpeg_format as jf
+    from cassmantle_amd.ops._ext import ext
+    B, H, W, _ = t.shape
+    _, nb, mx, my = jf.geometry(H, W, "420")
+    nint = -(-mx * my // restart)
+    tables, header = ops._jpeg_plan(t.device, H, W, QUALITY, "420", restart)
+    coef = torch.empty((B, mx * my, nb, 64), device="cuda", dtype=torch.int16)
+    work = torch.empty(2 * B * nint + B + 1, device="cuda", dtype=torch.int32)
+    ext().jpeg_count(t, tables, header, coef, work, 1, restart)
+    planes = torch.empty(coef.numel(), device="cuda", dtype=torch.uint8)
+    out = torch.empty((B, H, W, 3), device="cuda", dtype=torch.uint8)
+    best = 1e9
+    for _ in range(iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        ext().jpeg_reconstruct(coef, tables, planes, out, H, W, 1)
+        e1.record()
+        torch.cuda.synchronize()
+        best = min(best, e0.elapsed_time(e1))
+    return best
+
+
+def content_main(a, emit) -> int:
+    import numpy as np
+    import torch
+    from PIL import Image
+    from cassmantle_amd.config import Config
+    from cassmantle_amd.game.content import DeviceImage
+    from cassmantle_amd.game.imaging import encode_jpeg
+    from cassmantle_amd.runtime.factory import build_content_jpeg_fn
+
+    def psnr(x, y):
+        mse = float(np.mean((x.astype(np.float64) - y.astype(np.float64)) ** 2))
+        return round(10 * np.log10(255.0 ** 2 / max(mse, 1e-9)), 2)
+
+    def new_fn(restart_mcus):
+        c = Config()
+        c.model.gpu_jpeg = c.model.gpu_jpeg_content = True
+        c.model.jpeg_restart_mcus = restart_mcus
+        return build_content_jpeg_fn(c, "cuda")
+
+    for res in a.res:
+        img = source_image(res).copy()
+        t = torch.from_numpy(img).cuda()
+        mcu_row = (res + 15) // 16
+
+        def run_parent():
+            dimg = DeviceImage(t)                    # fresh: no cached host copy
+            torch.cuda.synchronize()
+            w0, c0 = time.perf_counter(), time.process_time()
+            jpeg = encode_jpeg(dimg, QUALITY)
+            wall, cpu = time.perf_counter() - w0, time.process_time() - c0
+            dec = np.asarray(Image.open(io.BytesIO(jpeg)).convert("RGB"))
+            return {"res": res, "path": "parent", "wall_ms": round(wall * 1e3, 3), "cpu_ms": round(cpu * 1e3, 3),
+                    "d2h_bytes": res * res * 3, "jpeg_bytes": len(jpeg), "psnr_db": psnr(dec, img)}
+
+        def run_new(restart=0):                      # 0: the default, one MCU row per interval
+            fn = new_fn(restart)
+            restart = restart or mcu_row
+            dimg = DeviceImage(t)
+            torch.cuda.synchronize()
+            w0, c0 = time.perf_counter(), time.process_time()
+            jpeg, decoded = fn(dimg, QUALITY)
+            torch.cuda.synchronize()                 # to the end of the idct + colour kernels
+            wall, cpu = time.perf_counter() - w0, time.process_time() - c0
+            dec = decoded.tensor.cpu().numpy()
+            pil = np.asarray(Image.open(io.BytesIO(jpeg)).convert("RGB"))
+            return {"res": res, "path": "gpu_jpeg_content", "restart_mcus": restart,
+                    "wall_ms": round(wall * 1e3, 3), "cpu_ms": round(cpu * 1e3, 3),
+                    "d2h_bytes": len(jpeg) + 8, "jpeg_bytes": len(jpeg), "psnr_db": psnr(dec, img),
+                    "decoded_equals_pil_decode": bool(np.array_equal(dec, pil)), "host_copy_made": dimg._host is not None}
+
+        run_parent()
+        run_new()
+        pil_size = None
+        for rep in range(a.reps):
+            p = run_parent()
+            pil_size = p["jpeg_bytes"]
+            emit(dict(p, rep=rep))
+            n = run_new()
+            emit(dict(n, rep=rep, size_vs_pil=round(n["jpeg_bytes"] / pil_size, 4)))
+        for restart in (4, 16):                      # shorter intervals: more lanes code, more bytes
+            run_new(restart)
+            n = run_new(restart)
+            emit(dict(n, sweep=True, size_vs_pil=round(n["jpeg_bytes"] / pil_size, 4)))
+        emit({"res": res, "reconstruct_device_ms": round(reconstruct_device_ms(t[None].contiguous(), mcu_row), 4),
+              "kernels": "jpeg_idct_kernel + jpeg_colour_kernel"})
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=int, nargs="+", default=[512, 1024])
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--out", default=None, help="also append the JSON records to this file")
+    ap.add_argument("--content", action="store_true", help="the content JPEG of one new image (see above)")
     a = ap.parse_args(argv)
     import numpy as np
     import torch
@@ -105,6 +216,11 @@ def main(argv=None) -> int:
             sink.write(line + "\n")
             sink.flush()
 
+    if a.content:
+        rc = content_main(a, emit)
+        if sink:
+            sink.close()
+        return rc
     for res in a.res:
         img = source_image(res).copy()
         jpeg = encode_jpeg(img, QUALITY)
