@@ -134,6 +134,12 @@ class ModelConfig:
     # whether a front-end still holds the device image or decodes the stored JPEG (the reference
     # blurs the decoded JPEG, src/server.py:53-56).  Needs gpu_jpeg and gpu_blur
     gpu_jpeg_content: bool = False
+    # the GPU blur itself: gaussian (a true fp32 Gaussian, ops.gaussian_blur) | pil (Pillow's
+    # GaussianBlur = three integer box passes per axis, bit for bit: ops.gaussian_blur_pil).  With
+    # pil the masked pixels are those blur_pil gives on a CPU front-end and those of the reference
+    # (src/backend.py:322-324), and a gpu_jpeg prewarm blurs every bucket in one launch.
+    # gaussian: today's bytes
+    blur_kernel: str = "gaussian"
     use_graphs: bool = True               # hipGraph-captured denoise loop
     fp8_attention: bool = False           # BASELINE config 4 (SDXL)
     weights_path: Optional[str] = None    # diffusers-layout dir (unet/ vae/ text_encoder[_2]/ *.safetensors)

@@ -747,6 +747,76 @@ def gaussian_blur(img: torch.Tensor, sigma: float) -> torch.Tensor:
     return out
 
 
+_BLUR_PIL_PLANS: dict = {}     # (device, radii) -> (device table of the tiled rows | None, their largest r, general rows)
+
+
+def _blur_pil_plan(device, radii: tuple):
+    """The box parameters of ``radii`` (ops.reference.box_params; radius <= 0: the identity box):
+    rows (r, ww, fw, slot) with r within the tiled kernel's reach as one int32 device table,
+    uploaded once per key, the others as host tuples for the general path."""
+    from . import blur_format as bf
+    key = (device, radii)
+    plan = _BLUR_PIL_PLANS.get(key)
+    if plan is None:
+        rmax_tiled = ext().blur_pil_max_tiled_radius()
+        rows = [(*(bf.box_params(r) if r > 0 else bf.IDENTITY), i) for i, r in enumerate(radii)]
+        tiled = [row for row in rows if row[0] <= rmax_tiled]
+        general = [row for row in rows if row[0] > rmax_tiled]
+        table = torch.tensor(tiled, dtype=torch.int32).to(device) if tiled else None
+        if len(_BLUR_PIL_PLANS) >= 64:
+            _BLUR_PIL_PLANS.clear()
+        plan = _BLUR_PIL_PLANS[key] = (table, max((row[0] for row in tiled), default=0), general)
+    return plan
+
+
+def gaussian_blur_pil(img, radii, out: Optional[torch.Tensor] = None):
+    """``PIL.ImageFilter.GaussianBlur`` of a uint8 ``[H, W, 3]`` image (a tensor, or a
+    ``DeviceImage``), bit for bit what Pillow and ``ops.reference.gaussian_blur_pil`` give (the
+    contract: ops/csrc/blur_pil.hip).  A scalar radius gives ``[H, W, 3]``, a sequence ``[n, H, W,
+    3]`` (radius <= 0: a copy of the input in its slot).  ``out``: a contiguous uint8 buffer of
+    that shape (or with more slices, which stay untouched) on the image's device, written in
+    place and returned.
+
+    HIP path, all on the current stream: every radius whose box radius the tiled kernel covers
+    (<= 15, Gaussian radius up to ~16.5) is one z-slice of ONE launch that stores straight into
+    its slice of the buffer; a larger radius takes six one-pass launches through two scratch
+    images.  The parameter table is uploaded once per (device, radii)."""
+    t = getattr(img, "tensor", img)
+    if not isinstance(t, torch.Tensor):
+        if out is not None:
+            raise ValueError("gaussian_blur_pil: out= needs a tensor image")
+        return ref.gaussian_blur_pil(img, radii)
+    if t.dim() != 3 or t.shape[-1] != 3 or t.dtype != torch.uint8 or t.numel() == 0:
+        raise ValueError("gaussian_blur_pil: uint8 [H, W, 3] expected")
+    scalar = isinstance(radii, (int, float))
+    rs = (float(radii),) if scalar else tuple(float(r) for r in radii)
+    n = len(rs)
+    buf = None
+    if out is not None:
+        buf = out[None] if (scalar and out.dim() == 3) else out
+        if (buf.dim() != 4 or buf.dtype != torch.uint8 or buf.device != t.device or not buf.is_contiguous()
+                or buf.shape[0] < n or tuple(buf.shape[1:]) != tuple(t.shape)):
+            raise ValueError("gaussian_blur_pil: out must be a contiguous uint8 [n, H, W, 3] buffer on the image's device")
+    if not _use_hip(t):
+        res = ref.gaussian_blur_pil(t, rs)
+        if buf is not None:
+            buf[:n].copy_(res)
+    else:
+        x = t.contiguous()
+        res = buf if buf is not None else torch.empty((n, *x.shape), device=x.device, dtype=torch.uint8)
+        if n:
+            table, rmax, general = _blur_pil_plan(x.device, rs)
+            if table is not None:
+                ext().blur_pil_tiled(x, table, res, rmax)
+            if general:
+                scratch = torch.empty((2, *x.shape), device=x.device, dtype=torch.uint8)
+                for r, ww, fw, slot in general:
+                    ext().blur_pil_general(x, res, slot, scratch, r, ww, fw)
+    if out is not None:
+        return out if (out.dim() == 3 or out.shape[0] == n) else out[:n]
+    return res[0] if scalar else res
+
+
 _JPEG_PLANS: dict = {}     # (device, H, W, quality, sampling, restart_mcus) -> (tables, header) on the device
 
 

@@ -943,6 +943,53 @@ void jpeg_reconstruct(const at::Tensor& coef, const at::Tensor& tables, at::Tens
   launch_jpeg_reconstruct(a, cur_stream());
 }
 
+// PIL's GaussianBlur (blur contract: blur_pil.hip).  img uint8 [H, W, 3]; out uint8 [N, H, W, 3].
+void blur_pil_check(const at::Tensor& img, const at::Tensor& out) {
+  CHECK_DEV(img); CHECK_CONTIG(img); CHECK_DEV(out); CHECK_CONTIG(out);
+  TORCH_CHECK(img.scalar_type() == at::kByte && img.dim() == 3 && img.size(2) == 3 && img.numel() > 0,
+              "blur_pil: img uint8 [H, W, 3]");
+  TORCH_CHECK(img.size(0) < 65536 && img.size(1) < 65536, "blur_pil: image sides must be below 65536");
+  TORCH_CHECK(out.scalar_type() == at::kByte && out.dim() == 4 && out.size(0) > 0 && out.size(1) == img.size(0) &&
+              out.size(2) == img.size(1) && out.size(3) == 3, "blur_pil: out uint8 [N, H, W, 3]");
+  TORCH_CHECK(out.device() == img.device(), "blur_pil: img and out on one device");
+  // every pass reads its source while other lanes store: the source image is never a destination
+  const char* i0 = static_cast<const char*>(img.data_ptr());
+  const char* o0 = static_cast<const char*>(out.data_ptr());
+  TORCH_CHECK(i0 + img.numel() <= o0 || o0 + out.numel() <= i0, "blur_pil: out overlaps img");
+}
+
+// table int32 [n, 4] = (r, ww, fw, slot) on the device, every r <= rmax: row z -> out[slot]
+// (the kernel skips a row whose r or slot is out of range, so no store can leave out)
+void blur_pil_tiled(const at::Tensor& img, const at::Tensor& table, at::Tensor& out, int64_t rmax) {
+  blur_pil_check(img, out);
+  CHECK_DEV(table); CHECK_CONTIG(table);
+  TORCH_CHECK(table.scalar_type() == at::kInt && table.dim() == 2 && table.size(1) == 4 && table.size(0) > 0 &&
+              table.size(0) < 65536 && table.device() == img.device(), "blur_pil: table int32 [n, 4], n < 65536");
+  TORCH_CHECK(rmax >= 0 && rmax <= blur_pil_max_tiled_radius(), "blur_pil: the tiled kernel covers box radius <= ",
+              blur_pil_max_tiled_radius());
+  launch_blur_pil_tiled(img.data_ptr<uint8_t>(), (int)img.size(0), (int)img.size(1), table.data_ptr<int>(),
+                        (int)table.size(0), (int)rmax, (int)out.size(0), out.data_ptr<uint8_t>(), cur_stream());
+}
+
+// any box radius into out[slot]; scratch uint8 [2, H, W, 3]
+void blur_pil_general(const at::Tensor& img, at::Tensor& out, int64_t slot, at::Tensor& scratch, int64_t r,
+                      int64_t ww, int64_t fw) {
+  blur_pil_check(img, out);
+  blur_pil_check(img, scratch);
+  TORCH_CHECK(scratch.size(0) == 2, "blur_pil: scratch uint8 [2, H, W, 3]");
+  TORCH_CHECK(slot >= 0 && slot < out.size(0), "blur_pil: slot outside out");
+  const int64_t one = (int64_t)1 << 24;
+  TORCH_CHECK(r >= 0 && r < 32768 && ww >= 0 && fw >= 0 && (2 * r + 1) * ww + 2 * fw <= one,
+              "blur_pil: box weights must sum to at most 2^24");
+  const char* s0 = static_cast<const char*>(scratch.data_ptr());
+  const char* o0 = static_cast<const char*>(out.data_ptr());
+  TORCH_CHECK(s0 + scratch.numel() <= o0 || o0 + out.numel() <= s0, "blur_pil: scratch overlaps out");
+  const int64_t n = img.numel();
+  uint8_t* sp = scratch.data_ptr<uint8_t>();
+  launch_blur_pil_general(img.data_ptr<uint8_t>(), (int)img.size(0), (int)img.size(1), (int)r, (uint32_t)ww,
+                          (uint32_t)fw, sp, sp + n, out.data_ptr<uint8_t>() + slot * n, cur_stream());
+}
+
 }  // namespace
 
 using nogil = py::call_guard<py::gil_scoped_release>;
@@ -987,6 +1034,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("cosine_topk", &cosine_topk, nogil());
   m.def("mean_pool_l2", &mean_pool_l2, nogil());
   m.def("gaussian_blur", &gaussian_blur, nogil());
+  m.def("blur_pil_tiled", &blur_pil_tiled, nogil());
+  m.def("blur_pil_general", &blur_pil_general, nogil());
+  m.def("blur_pil_max_tiled_radius", []() { return (int64_t)blur_pil_max_tiled_radius(); });
   m.def("to_uint8", &to_uint8, nogil());
   m.def("jpeg_count", &jpeg_count, nogil());
   m.def("jpeg_write", &jpeg_write, nogil());

@@ -238,3 +238,13 @@ void launch_jpeg_write(const JpegArgs& a, hipStream_t s);
 // inverse DCT of coef into planes, then upsampling + colour into dec (reads B, H, W, nb, mx, my,
 // qtab, coef only)
 void launch_jpeg_reconstruct(const JpegArgs& a, hipStream_t s);
+
+// PIL's GaussianBlur, bit for bit (blur_pil.hip; blur contract in its header comment)
+int blur_pil_max_tiled_radius();
+// table int32 [n][4] = (r, ww, fw, slot) on the device, every r <= rmax <= blur_pil_max_tiled_radius():
+// row z blurs img [H][W][3] into out[slot] of out [nslots][H][W][3]
+void launch_blur_pil_tiled(const uint8_t* img, int H, int W, const int* table, int n, int rmax, int nslots,
+                           uint8_t* out, hipStream_t s);
+// any box radius: six one-pass launches img -> s1 -> s2 -> ... -> out, all [H][W][3]
+void launch_blur_pil_general(const uint8_t* img, int H, int W, int r, uint32_t ww, uint32_t fw, uint8_t* s1,
+                             uint8_t* s2, uint8_t* out, hipStream_t s);

@@ -77,13 +77,37 @@ def build_scorer(cfg: Config, device: Optional[str] = None, wrap=None):
     return BatchingScorer(backend, cfg.game.min_score, window_ms=cfg.model.scorer_batch_window_ms)
 
 
+def blur_kernel(cfg: Config) -> str:
+    """``ModelConfig.blur_kernel``: gaussian (ops.gaussian_blur) | pil (ops.gaussian_blur_pil, the
+    bytes of PIL's GaussianBlur); anything else is an error, not the default."""
+    k = str(cfg.model.blur_kernel).lower()
+    if k not in ("gaussian", "pil"):
+        raise ValueError(f"blur_kernel={cfg.model.blur_kernel!r}: expected gaussian or pil")
+    return k
+
+
+def _device_pixels(img, dev: str) -> torch.Tensor:
+    """The pixels of ``img`` on ``dev``: a DeviceImage is already in this GPU's HBM, anything else
+    (an array, a PIL decode) is uploaded."""
+    t = getattr(img, "tensor", None)
+    if t is not None and t.device.type == "cuda":
+        return t.to(dev, non_blocking=False)
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(img))).to(dev, non_blocking=False)
+
+
 def build_blur_fn(cfg: Config, device: Optional[str] = None):
     """The /fetch/contents blur (``mask_image``, ``src/backend.py:322-324``) on the GPU: the HIP
-    LDS-tiled Gaussian (ops.gaussian_blur) on its own stream.  ``None`` -> PIL on the CPU."""
+    LDS-tiled Gaussian (ops.gaussian_blur) on its own stream, or with ``blur_kernel=pil`` PIL's own
+    GaussianBlur bit for bit (ops.gaussian_blur_pil).  ``None`` -> PIL on the CPU."""
     dev = device or ("cuda" if torch.cuda.is_available() else "cpu")
+    kernel = blur_kernel(cfg)
     if not cfg.model.gpu_blur or not dev.startswith("cuda"):
         return None
     from .. import ops
+    if kernel == "pil":
+        def blur_exact(img, radius: float):
+            return ops.gaussian_blur_pil(_device_pixels(img, dev), float(radius)).cpu().numpy()
+        return blur_exact
     # the blur runs on the calling thread's current stream: a stream of its own in a process that
     # shares its GPU with a generation worker cost that worker 14 % of its images/s
     # (profiles/r6_live_ipc_stream_ab.txt); CASSMANTLE_BLUR_STREAM=own restores one
@@ -104,13 +128,22 @@ def build_blur_fn(cfg: Config, device: Optional[str] = None):
 def build_blur_jpeg_fn(cfg: Config, device: Optional[str] = None):
     """Blur + JPEG of a whole set of radii on the GPU (``gpu_jpeg``): ``fn(img, radii, quality)
     -> [bytes]``.  Each radius is blurred by ops.gaussian_blur into one ``[len(radii), H, W, 3]``
-    buffer, which one ops.jpeg_encode call encodes: the entropy-coded bytes cross to the host,
+    buffer (``blur_kernel=pil``: ONE ops.gaussian_blur_pil call is that buffer), which one
+    ops.jpeg_encode call encodes: the entropy-coded bytes cross to the host,
     not the pixels.  Everything runs on the calling thread's current stream (see build_blur_fn).
     ``None`` unless ``gpu_jpeg`` and ``gpu_blur`` are set and the device is a GPU."""
     dev = device or ("cuda" if torch.cuda.is_available() else "cpu")
+    kernel = blur_kernel(cfg)
     if not (cfg.model.gpu_jpeg and cfg.model.gpu_blur) or not str(dev).startswith("cuda"):
         return None
     from .. import ops
+    if kernel == "pil":
+        def blur_jpeg_exact(img, radii: Sequence[float], quality: int):
+            x = _device_pixels(img, dev)
+            buf = ops.gaussian_blur_pil(x, [float(r) for r in radii])      # ONE launch: [len(radii), H, W, 3]
+            restart = cfg.model.jpeg_restart_mcus or (x.shape[1] + 15) // 16      # 0: one MCU row
+            return ops.jpeg_encode(buf, quality=quality, restart_mcus=restart)
+        return blur_jpeg_exact
 
     def blur_jpeg(img, radii: Sequence[float], quality: int):
         t = getattr(img, "tensor", None)        # DeviceImage: already in this GPU's HBM

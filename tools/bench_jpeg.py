@@ -26,6 +26,14 @@ PSNR of its decoded pixels against the original, and for the new path the device
 decoded pixels equal PIL's decode of the bytes.
 
     python tools/bench_jpeg.py --content [--res 512 1024] [--reps 2] [--out profiles/jpeg_content.jsonl]
+
+``--blur-kernel pil`` runs the prewarm comparison with a third row, ``gpu_jpeg`` + ``blur_kernel=pil``
+(one batched ops.gaussian_blur_pil launch, ops/csrc/blur_pil.hip, instead of 60 Gaussian
+launches and 60 copies), the three paths interleaved ``--reps`` times after a warm-up of each.  It also records the device time of
+the blur stage alone (HIP events around the 60 Gaussian launches + copies, and around the one
+batched launch) and whether the batched blur equals Pillow's GaussianBlur on this image.
+
+    python tools/bench_jpeg.py --blur-kernel pil [--res 512 1024] [--reps 2] [--out profiles/blur_pil_prewarm.jsonl]
 """
 import argparse
 import io
@@ -120,6 +128,79 @@ def reconstruct_device_ms(t, restart: int, iters: int = 5) -> float:
     return best
 
 
+def blur_stage_device_ms(x, radii, iters: int = 5):
+    """Device time of the blur stage alone for one prewarm (HIP events; nothing else is queued), in
+    ms: the 60 ops.gaussian_blur launches + copies of build_blur_jpeg_fn, and the one batched
+    ops.gaussian_blur_pil launch."""
+    import torch
+    from cassmantle_amd import ops
+    buf = torch.empty((len(radii), *x.shape), device=x.device, dtype=torch.uint8)
+
+    def gaussian():
+        for i, r in enumerate(radii):
+            ops.copy_(buf[i], ops.gaussian_blur(x, float(r)))
+
+    def timed(fn):
+        best = 1e9
+        for _ in range(iters + 1):                   # the first round warms up
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            best = min(best, e0.elapsed_time(e1))
+        return round(best, 4)
+
+    return {"gaussian_60_launches_ms": timed(gaussian),
+            "pil_one_launch_ms": timed(lambda: ops.gaussian_blur_pil(x, radii, out=buf))}
+
+
+def blur_kernel_main(a, emit) -> int:
+    import numpy as np
+    import torch
+    from PIL import Image, ImageFilter
+    from cassmantle_amd import ops
+    from cassmantle_amd.config import Config
+    from cassmantle_amd.game.content import DeviceImage
+    from cassmantle_amd.game.imaging import encode_jpeg
+    from cassmantle_amd.runtime.factory import build_blur_fn, build_blur_jpeg_fn
+
+    for res in a.res:
+        img = source_image(res).copy()
+        jpeg = encode_jpeg(img, QUALITY)
+        dimg = DeviceImage(torch.from_numpy(img).cuda())
+        dimg.host()
+        blur_fn = build_blur_fn(Config(), "cuda")
+        radii = [i * BUCKET for i in range(1, int(MAX_BLUR / BUCKET) + 1)]
+
+        def jpeg_fn(kernel):
+            c = Config()
+            c.model.gpu_jpeg, c.model.blur_kernel = True, kernel
+            return build_blur_jpeg_fn(c, "cuda")
+
+        fns = {"parent": None, "gpu_jpeg": jpeg_fn("gaussian"), "gpu_jpeg+blur_kernel=pil": jpeg_fn("pil")}
+
+        def run(path, tag):
+            n, wall, cpu, outs = prewarm_once(blur_fn, fns[path], dimg, jpeg, tag)
+            size = sum(len(v) for r, v in outs.items() if r > 0)
+            return {"res": res, "path": path, "buckets": n, "wall_ms": round(wall * 1e3, 2),
+                    "cpu_ms": round(cpu * 1e3, 2), "jpeg_bytes": size,
+                    "d2h_bytes": (n - 1) * res * res * 3 if path == "parent" else size + 4 * n}
+
+        for path in fns:
+            run(path, f"warm-{path}")
+        for rep in range(a.reps):
+            for path in fns:
+                emit(dict(run(path, f"{path}-{rep}"), rep=rep))
+        got = ops.gaussian_blur_pil(dimg.tensor, [0.25, 7.5, 15.0]).cpu().numpy()
+        same = all(np.array_equal(g, np.asarray(Image.fromarray(img).filter(ImageFilter.GaussianBlur(r))))
+                   for g, r in zip(got, (0.25, 7.5, 15.0)))
+        emit({"res": res, "check": "batched_blur_equals_pillow", "radii": [0.25, 7.5, 15.0], "equal": bool(same)})
+        emit(dict(blur_stage_device_ms(dimg.tensor, radii), res=res, stage="blur, device time (HIP events)"))
+    return 0
+
+
 def content_main(a, emit) -> int:
     import numpy as np
     import torch
@@ -194,6 +275,8 @@ def main(argv=None) -> int:
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--out", default=None, help="also append the JSON records to this file")
     ap.add_argument("--content", action="store_true", help="the content JPEG of one new image (see above)")
+    ap.add_argument("--blur-kernel", choices=["pil"], default=None,
+                    help="the prewarm comparison with blur_kernel=pil as a third row (see above)")
     a = ap.parse_args(argv)
     import numpy as np
     import torch
@@ -216,8 +299,8 @@ def main(argv=None) -> int:
             sink.write(line + "\n")
             sink.flush()
 
-    if a.content:
-        rc = content_main(a, emit)
+    if a.content or a.blur_kernel:
+        rc = content_main(a, emit) if a.content else blur_kernel_main(a, emit)
         if sink:
             sink.close()
         return rc
