@@ -7,6 +7,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_ext.h>
 
+#include "gemm_tiles.h"
 #include "kernels.h"
 
 namespace {
@@ -1009,6 +1010,15 @@ PYBIND11_MODULE(_C, m) {
   m.def("row_stats", &row_stats, nogil());
   m.def("gemm_cat", &gemm_cat, nogil());
   m.def("group_norm_cat", &group_norm_cat, nogil());
+  // the live tile configs (gemm_tiles.h): (id, family, BM, BN, waves "WMxWN", stages, producers, gated)
+  m.def("gemm_tile_menu", []() {
+    static const char* const fam[] = {"static", "pingpong", "deep", "areg"};
+    py::list rows;
+    for (const GemmTile& t : kGemmTiles)
+      rows.append(py::make_tuple(t.id, fam[t.family], t.BM, t.BN, std::to_string(t.WM) + "x" + std::to_string(t.WN), t.stages,
+                                 t.producers, t.gated()));
+    return rows;
+  });
   m.def("gemm_set_override", [](int64_t cfg, int64_t split) { gemm_set_override((int)cfg, (int)split); });
   m.def("gemm_tune_set", [](const std::string& key, int64_t cfg, int64_t split) { gemm_tune_set(key, (int)cfg, (int)split); });
   m.def("gemm_tune_clear", []() { gemm_tune_clear(); });

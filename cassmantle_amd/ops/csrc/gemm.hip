@@ -9,6 +9,7 @@
 #include <unordered_map>
 
 #include "common.h"
+#include "gemm_tiles.h"
 #include "kernels.h"
 
 void gemm_c0_buf_launch(const GemmArgs& p, float* ws, hipStream_t s);
@@ -23,65 +24,6 @@ void gemm_pp_c2_launch(const GemmArgs& p, float* ws, hipStream_t s);
 namespace {
 
 constexpr int BK = 64;
-
-// Tile menu.  4 waves, 2 blocks per CU by LDS, 2 stages:
-//   0: 128x128 (2x2)   1: 128x160 (2x2, wave 80x64)   2: 256x64 (4x1)   3: 128x64 (2x2)   4: 256x16 (4x1)
-// 8 waves, 1 block per CU, 3-stage ring:
-//   5: 256x160 (4x2, wave 64x80)   6: 256x128 (4x2, wave 64x64)
-// 8-wave ping-pong kernel (gemm_pp.h; 1 block per CU, 4 phases per k-tile, counted vmcnt):
-//   7: 256x256   8: 256x160   9: 256x128   10: 128x256
-// deep LDS ring (gemm_impl.h STAGES 3-5, one block per CU; buffer-resource modes, bf16 out):
-//   12: 128x128 4w S4 (also gated)   13: 128x64 4w S5   14: 128x160 8w S4
-//   15: A-in-registers short-K kernel (gemm_areg.hip: K = 320 / 640, W streamed in chunks)
-//   16: 128x80 4w (4x1, wave 32x80) S4: M = 2048 x N = 1280 is exactly 256 tiles, one per CU
-//       (the 128x64 tile's 320 blocks ran as 1.25 rounds; the deep rings are one block per CU)
-//   20: ping-pong 128x160 (4x2 waves, wave 32x80): twice the blocks of 256x160 without split-K
-//       (M = 8192 x N = 640: 256 tiles)
-//   21: ping-pong 128x128 (4x2 waves, wave 32x64, 64 KiB LDS: 2 blocks per CU)
-//   22: ping-pong 128x64 (4x2 waves, 48 KiB LDS)
-//   26 / 27: 8-wave 128x80 (8x1 waves, wave 16x80, 4-stage ring) / 128x64 (4x2 waves, 3 stages):
-//       the small-grid tiles with twice the waves issuing LDS-DMA.  A CU's LDS-DMA fill rate is
-//       set by the number of waves issuing it, not by the bytes in flight (4 waves: 22 B/cycle
-//       on the GEMM row pattern at any ring depth, 8 waves: 37; profiles/r3_lds_fill_probe.jsonl)
-//   31 / 32 / 33: warp-specialised deep rings, 8 MFMA waves + 8 DMA-only producer waves (1024
-//       threads, 4 stages): 128x80 (8x1), 128x64 (4x2), 128x160 (4x2).  (256x128 / 128x256 / 128x128
-//       and the gated 128x160 8x1 producer-wave tiles: bench-neutral in situ, removed;
-//       profiles/r4_producer_waves_ab.txt)
-// Removed in round 4 (measured, picked by no shape of the SD-1.5 / SDXL census; results kept in
-// profiles/ and in git history): 11 (128x160 4w S4), 17-19 (register-staged 4-wave tiles,
-// profiles/r2_regstage_ab.txt), 23 (ping-pong 256x64), 24/25 (halo-staged 3x3 conv,
-// profiles/r3_bench_halo.jsonl), 28 (16-wave 128x64, profiles/r3_probe_16wave.jsonl), 29/30 (8-wave
-// 128x128 / 256x80 and the gated 128x128, profiles/r3_tune_8wave_b_ab.txt,
-// profiles/r3_tune_8wave_gated.txt).  Their indices stay reserved so table keys keep their meaning.
-// Configs >= 11 are chosen only from the measured tuning table (gemm_tune_*) or when forced.
-struct TileCfg { int BM, BN; float eff; int slots; };
-constexpr int kNumTiles = 34;
-constexpr int kPP128 = 20, kPP128x128 = 21;
-// ping-pong configs outside the 7..10 block (dispatch and eligibility)
-constexpr bool is_pp_cfg(int c) { return (c >= 7 && c < 11) || c == 20 || c == 21 || c == 22; }
-// configs with a kernel behind them (the reserved indices above have none)
-constexpr bool is_live_cfg(int c) {
-  return (c >= 0 && c <= 10) || (c >= 12 && c <= 16) || (c >= 20 && c <= 22) || c == 26 || c == 27 ||
-         (c >= 31 && c <= 33);
-}
-constexpr int kAreg = 15;
-constexpr int kFirstPP = 7;
-constexpr int kFirstDeep = 11;
-// slots = resident blocks on the chip: 128x64 needs 48 KiB of LDS per block, so 3 blocks fit a
-// CU (768 slots); with 512 the model undercounted it and missed the measured best on the
-// level-2..4 plain GEMMs (profiles/r1_gemm_plan_sweep.jsonl: 14.5 vs 17.8 us at 8192x640x640)
-constexpr TileCfg kTiles[kNumTiles] = {{128, 128, 1.00f, 512}, {128, 160, 1.02f, 512}, {256, 64, 0.95f, 512},
-                                       {128, 64, 0.80f, 768},  {256, 16, 0.25f, 512},  {256, 160, 1.02f, 256},
-                                       {256, 128, 1.00f, 256}, {256, 256, 1.60f, 256}, {256, 160, 1.55f, 256},
-                                       {256, 128, 1.45f, 256}, {128, 256, 1.45f, 256}, {128, 160, 1.f, 256},
-                                       {128, 128, 1.f, 256},   {128, 64, 1.f, 256},    {128, 160, 1.f, 256},
-                                       {128, 64, 1.f, 256},    {128, 80, 1.f, 256},    {128, 64, 1.f, 768},
-                                       {128, 128, 1.f, 512},   {128, 160, 1.f, 512},   {128, 160, 1.f, 256},
-                                       {128, 128, 1.f, 512},   {128, 64, 1.f, 768},    {256, 64, 1.f, 512},
-                                       {256, 160, 1.f, 256},   {128, 160, 1.f, 256},   {128, 80, 1.f, 256},
-                                       {128, 64, 1.f, 256},    {128, 64, 1.f, 256},    {128, 128, 1.f, 256},
-                                       {256, 80, 1.f, 256},    {128, 80, 1.f, 256},    {128, 64, 1.f, 256},
-                                       {128, 160, 1.f, 256}};
 
 // buffer-resource LDS-DMA path: K in whole k-tiles and every byte range addressable by a
 // 31-bit buffer offset (num_records), plain GEMMs and Cin % 64 convolutions without upsample
@@ -144,19 +86,21 @@ __global__ void gemm_simt_kernel(GemmArgs p) {
     reinterpret_cast<uint16_t*>(p.C)[(long long)batch * p.sC + (long long)m * p.ldc + n] = f2bf(o);
 }
 
-// the ping-pong kernel takes the buffer-resource modes (plain / two-source A, Cin % 64 convs
-// without the fused upsample) with bf16 output
-bool pp_ok(const GemmArgs& p) {
-  // bf16 outputs the LDS-staged epilogue takes (the kernel's direct path only stores split-K slabs)
-  const int cbs = p.ldcb ? p.ldcb : p.N;
-  if (p.N % 8 != 0 || p.ldc % 8 != 0 || cbs % 4 != 0) return false;
-  if (p.out_f32 || !buf_ok(p) || p.K % BK != 0) return false;
-  if (p.conv && (p.upsample || p.Cin % 64 != 0)) return false;
-  return p.N > 16;
+// can a kernel family run this call?  The ping-pong and deep-ring kernels take the buffer-resource
+// modes (plain / two-source A, Cin % 64 convs without the fused upsample) with bf16 output; ping-pong
+// only the bf16 outputs the LDS-staged epilogue takes (its direct path only stores split-K slabs)
+bool family_runs(GemmTileFamily f, const GemmArgs& p) {
+  if (f == kTileStatic) return true;
+  if (f == kTileAreg) return gemm_areg_ok(p);
+  if (f == kTilePingPong && (p.N % 8 != 0 || p.ldc % 8 != 0 || (p.ldcb ? p.ldcb : p.N) % 4 != 0)) return false;
+  return !p.out_f32 && buf_ok(p) && p.K % BK == 0 && (!p.conv || (!p.upsample && p.Cin % 64 == 0)) && p.N > 16;
 }
 
-bool deep_ok(const GemmArgs& p) {
-  return !p.out_f32 && buf_ok(p) && p.K % BK == 0 && (!p.conv || (!p.upsample && p.Cin % 64 == 0)) && p.N > 16;
+// a config is only taken -- from the tuning table or forced -- if it is live and its family can run
+// the call, so a stale table never selects an unsupported path
+bool cfg_runs(int cfg, const GemmArgs& p) {
+  const GemmTile* t = gemm_tile(cfg);
+  return t != nullptr && family_runs(t->family, p);
 }
 
 // ---- measured per-shape tuning table (tools/autotune_gemm.py -> ops/gemm_tuning.json, loaded by
@@ -220,7 +164,7 @@ GemmPlan gemm_plan(const GemmArgs& p) {
   if (p.row_stats != nullptr) {
     // output row statistics exist only in the shared LDS-staged epilogue (tile_epilogue):
     // no split-K, not the A-in-registers kernel
-    if (r.cfg == kAreg) r.cfg = 3;
+    if (r.cfg == kGemmAregTile) r.cfg = 3;
     r.split = 1;
   }
   g_last_plan = r;
@@ -242,10 +186,10 @@ static GemmPlan gemm_plan_impl(const GemmArgs& p) {
   if (g_record_key) g_last_key = gemm_key(p);
   // in-kernel LayerNorm statistics exist only in the A-in-registers kernel (the binding checked
   // eligibility, so neither the table nor a forced config may pick anything else)
-  if (p.ln_wsum != nullptr && p.ln_rows == nullptr && p.ln_rows_fx == nullptr) return GemmPlan{kAreg, 1};
+  if (p.ln_wsum != nullptr && p.ln_rows == nullptr && p.ln_rows_fx == nullptr) return GemmPlan{kGemmAregTile, 1};
   // GroupNorm folded into the A rows: only the A-in-registers kernel applies it (the binding
   // checked eligibility)
-  if (p.gn_stats != nullptr) return GemmPlan{kAreg, 1};
+  if (p.gn_stats != nullptr) return GemmPlan{kGemmAregTile, 1};
   if (force_cfg < 0) {
     bool have = false;
     GemmPlan tp{0, 1};
@@ -256,35 +200,31 @@ static GemmPlan gemm_plan_impl(const GemmArgs& p) {
         if (it != g_tune.end()) { tp = it->second; have = true; }
       }
     }
-    // a table entry is only taken if the kernel family can run this call (same checks as a
-    // forced config), so a stale table never selects an unsupported path
-    const bool elig = is_live_cfg(tp.cfg) &&
-                      (tp.cfg < kFirstPP || (is_pp_cfg(tp.cfg) ? pp_ok(p) : (tp.cfg == kAreg ? gemm_areg_ok(p) : deep_ok(p))));
-    if (have && elig) return tp;
+    if (have && cfg_runs(tp.cfg, p)) return tp;
   }
   static const int use_big = env_int("CASSMANTLE_GEMM_8WAVE", 0);
   const bool gated = p.act == ACT_GEGLU || p.act == ACT_SWIGLU;
   int only = -1;                         // forced tile (cost model still picks the split)
-  const bool pp_elig = pp_ok(p);
   // CASSMANTLE_GEMM_PP=0 keeps the planner on the 4-wave kernel (A/B knob); forced configs
   // (CASSMANTLE_GEMM_CFG / gemm_set_override) only need eligibility
   static const int pp_auto = env_int("CASSMANTLE_GEMM_PP", 0);
-  const bool pp = pp_elig && pp_auto;
-  const bool deep_elig = deep_ok(p);
-  if (force_cfg == kAreg) {
-    if (gemm_areg_ok(p)) return GemmPlan{kAreg, 1};
-  } else if (force_cfg >= 0 && is_live_cfg(force_cfg) && ((force_cfg == 4) == (p.N <= 16)) &&
-      (force_cfg < kFirstPP || (is_pp_cfg(force_cfg) ? pp_elig : deep_elig))) {
-    if (gated) {
-      if (force_cfg == 0 || force_cfg == 6) best.cfg = force_cfg;
-      else if (force_cfg >= kFirstDeep) best.cfg = 12;    // the deep-ring gated tile
-      else if (force_cfg >= kFirstPP) best.cfg = force_cfg == 8 ? 8 : 9;   // the ping-pong gated tiles
-      return best;
+  const bool pp = pp_auto && family_runs(kTilePingPong, p);
+  if (force_cfg >= 0 && cfg_runs(force_cfg, p)) {
+    const GemmTile& ft = *gemm_tile(force_cfg);
+    if (ft.family == kTileAreg) return GemmPlan{ft.id, 1};
+    if ((ft.BN <= 16) == (p.N <= 16)) {   // the N <= 16 tile takes those shapes and no others
+      if (gated) {
+        // a tile without a gated instantiation maps to a gated default: its family's, or for the
+        // table-only tiles (ping-pong 20-22 too, whose eligibility implies it) the deep ring's
+        best.cfg = ft.gated() ? ft.id : gemm_default_tile(ft.model ? ft.family : kTileDeep, true);
+        return best;
+      }
+      only = ft.id;
     }
-    only = force_cfg;
   }
   if (gated) {
-    if (pp && (p.N % 64 == 0) && (long long)(p.N / 64) * ((p.M + 255) / 256) >= 256) best.cfg = 9;
+    if (pp && (p.N % 64 == 0) && (long long)(p.N / 64) * ((p.M + 255) / 256) >= 256)
+      best.cfg = gemm_default_tile(kTilePingPong, true);
     return best;
   }
   const int nk = (p.K + BK - 1) / BK;
@@ -292,14 +232,12 @@ static GemmPlan gemm_plan_impl(const GemmArgs& p) {
   // (batched calls -- the upsampling conv's 4 parity classes -- split per batch: slabs [z][split])
   const bool can_split = p.N % 4 == 0 && p.K % 8 == 0 && p.M > 8;
   double best_t = 1e30;
-  for (int c = 0; c < kNumTiles; ++c) {
-    const TileCfg& tc = kTiles[c];
-    if (only >= 0 ? c != only : ((c == 5 || c == 6) && !use_big)) continue;
-    if (c >= kFirstDeep && only != c) continue;   // table / forced only
-    if (c == kAreg) continue;
-    if (c >= kFirstPP && c < kFirstDeep && !(only >= 0 ? pp_elig : pp)) continue;
-    if (c == 4 && p.N > 16) continue;
-    if (c != 4 && p.N <= 16) continue;
+  for (const GemmTile& tc : kGemmTiles) {   // ascending ids: the first of equal times wins
+    if (only >= 0 ? tc.id != only
+                  : !tc.model || (tc.family == kTileStatic && tc.WM * tc.WN == 8 && !use_big) ||
+                        (tc.family == kTilePingPong && !pp))
+      continue;
+    if ((tc.BN <= 16) != (p.N <= 16)) continue;
     const long long tiles = (long long)((p.N + tc.BN - 1) / tc.BN) * ((p.M + tc.BM - 1) / tc.BM) * p.batch;
     const double waste = (double)tc.BN * ((p.N + tc.BN - 1) / tc.BN) / p.N;   // padded columns
     for (int split = 1; split <= GEMM_MAX_SPLIT; ++split) {
@@ -314,7 +252,7 @@ static GemmPlan gemm_plan_impl(const GemmArgs& p) {
       // split-K: slab write + read at ~3 TB/s plus the extra reduce launch (~6 us in a graph)
       if (split > 1) t += 6.0 + 2.0 * (double)split * p.batch * p.M * p.N * 4 / 3.0e6;
       if (only >= 0 && force_split > 0 && split != force_split) continue;
-      if (t < best_t - 1e-9) { best_t = t; best = GemmPlan{c, split}; }
+      if (t < best_t - 1e-9) { best_t = t; best = GemmPlan{tc.id, split}; }
     }
   }
   return best;
@@ -338,11 +276,13 @@ void launch_gemm(const GemmArgs& p, float* ws, hipStream_t s) {
     return;
   }
   const bool buf = buf_ok(p);
-  if (p.cfg == kAreg && gemm_areg_ok(p)) {
+  const GemmTile* t = gemm_tile(p.cfg);
+  const GemmTileFamily fam = t != nullptr ? t->family : kTileStatic;
+  if (fam == kTileAreg && gemm_areg_ok(p)) {
     launch_gemm_areg(p, s);
     return;
   }
-  if (is_pp_cfg(p.cfg) && pp_ok(p)) {
+  if (fam == kTilePingPong && family_runs(fam, p)) {
     if (!p.conv) gemm_pp_c0_launch(p, ws, s);
     else gemm_pp_c2_launch(p, ws, s);
     return;

@@ -34,6 +34,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "gemm_tiles.h"
 #include "kernels.h"
 
 #ifndef GEMM_DIAG_APRO
@@ -1053,8 +1054,8 @@ void launch_t(const GemmArgs& p, float* ws, hipStream_t s) {
   // lambda inside this function template was left uninstantiated by hipcc)
   auto* kfn = &gemm_kernel<BM, BN, WM, WN, CONV, GEGLU, OUTF32, STAGES, BUF, NP>;
   if constexpr (lds > 65536) {
-    // > 64 KiB dynamic LDS must be opted into once (first call happens before any graph capture)
-    // > 64 KiB dynamic LDS opt-in, once per process (thread-safe static init)
+    // > 64 KiB dynamic LDS opt-in, once per process (thread-safe static init; the first call
+    // happens before any graph capture)
     static const bool once = [&] {
       (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       return true;
@@ -1065,62 +1066,34 @@ void launch_t(const GemmArgs& p, float* ws, hipStream_t s) {
   if (split > 1) launch_splitk_reduce<OUTF32>(p, ws, split, s);
 }
 
-template <int BM, int BN, int WM, int WN, int CONV, bool GEGLU, bool OUTF32, bool BUF>
-void launch_st(const GemmArgs& p, float* ws, hipStream_t s) {
-  if constexpr (WM * WN == 8) {
-    launch_t<BM, BN, WM, WN, CONV, GEGLU, OUTF32, 3, BUF>(p, ws, s);
-  } else {
-    // (4-wave tiles: STAGES=3 at one block/CU measured 1.3-1.7x SLOWER than 2 stages at 2
-    // blocks/CU on every SD shape, profiles/r1_ops_stages_ab.txt)
-    launch_t<BM, BN, WM, WN, CONV, GEGLU, OUTF32, 2, BUF>(p, ws, s);
+// Row I of the tile menu (gemm_tiles.h) in this translation unit's A-operand mode: launches and
+// returns true if it is config `cfg` and has an instantiation here (static tiles: every mode; deep
+// rings: buffer-resource modes with bf16 out; gated calls: the rows with a gated wave layout).
+// (4-wave static tiles: STAGES=3 at one block/CU measured 1.3-1.7x SLOWER than 2 stages at 2
+// blocks/CU on every SD shape, profiles/r1_ops_stages_ab.txt)
+template <int I, int CONV, bool GEGLU, bool OUTF32, bool BUF>
+bool launch_row(int cfg, const GemmArgs& p, float* ws, hipStream_t s) {
+  constexpr GemmTile t = kGemmTiles[I];
+  if constexpr ((t.family == kTileStatic || (t.family == kTileDeep && BUF && !OUTF32)) && (!GEGLU || t.gated())) {
+    if (t.id != cfg) return false;
+    launch_t<t.BM, t.BN, GEGLU ? t.GWM : t.WM, GEGLU ? t.GWN : t.WN, CONV, GEGLU, OUTF32, t.stages, BUF, t.producers>(p, ws, s);
+    return true;
   }
+  return false;
 }
 
-template <int CONV, bool OUTF32, bool BUF>
-void launch_cfg(const GemmArgs& p, float* ws, hipStream_t s) {
-  // deep-ring tiles (buffer-resource modes, bf16 out): one block per CU, STAGES-2 k-tiles ahead
-  if constexpr (BUF && !OUTF32) {
-    switch (p.cfg) {
-      case 12: return launch_t<128, 128, 2, 2, CONV, false, false, 4, true>(p, ws, s);
-      case 13: return launch_t<128, 64, 2, 2, CONV, false, false, 5, true>(p, ws, s);
-      case 14: return launch_t<128, 160, 4, 2, CONV, false, false, 4, true>(p, ws, s);
-      case 16: return launch_t<128, 80, 4, 1, CONV, false, false, 4, true>(p, ws, s);
-      case 26: return launch_t<128, 80, 8, 1, CONV, false, false, 4, true>(p, ws, s);
-      case 27: return launch_t<128, 64, 4, 2, CONV, false, false, 3, true>(p, ws, s);
-      // warp-specialised: 8 MFMA waves + 8 DMA-only producer waves (1024 threads)
-      case 31: return launch_t<128, 80, 8, 1, CONV, false, false, 4, true, 8>(p, ws, s);
-      case 32: return launch_t<128, 64, 4, 2, CONV, false, false, 4, true, 8>(p, ws, s);
-      case 33: return launch_t<128, 160, 4, 2, CONV, false, false, 4, true, 8>(p, ws, s);
-      // (256x128 / 128x256 / 128x128 and 128x160 8x1 (also gated) producer-wave tiles were tuned
-      // in situ in round 4: bench-neutral, removed; profiles/r4_producer_waves_ab.txt.  6-stage
-      // rings of 31 / 32: no faster with weights from HBM on every call,
-      // profiles/r4_cold_weight_probe.jsonl.  31-33 with the MFMA waves staging too: 3-15 % slower
-      // per call, bench-neutral, profiles/r4_producer_waves_ab.txt)
-      default: break;
-    }
-  }
-  switch (p.cfg) {
-    case 1: launch_st<128, 160, 2, 2, CONV, false, OUTF32, BUF>(p, ws, s); break;
-    case 2: launch_st<256, 64, 4, 1, CONV, false, OUTF32, BUF>(p, ws, s); break;
-    case 3: launch_st<128, 64, 2, 2, CONV, false, OUTF32, BUF>(p, ws, s); break;
-    case 4: launch_st<256, 16, 4, 1, CONV, false, OUTF32, BUF>(p, ws, s); break;
-    case 5: launch_st<256, 160, 4, 2, CONV, false, OUTF32, BUF>(p, ws, s); break;
-    case 6: launch_st<256, 128, 4, 2, CONV, false, OUTF32, BUF>(p, ws, s); break;
-    default: launch_st<128, 128, 2, 2, CONV, false, OUTF32, BUF>(p, ws, s); break;
-  }
+// a config without an instantiation here lands on the static default tile
+template <int CONV, bool GEGLU, bool OUTF32, bool BUF, int... I>
+void launch_cfg(const GemmArgs& p, float* ws, hipStream_t s, std::integer_sequence<int, I...>) {
+  if (!(launch_row<I, CONV, GEGLU, OUTF32, BUF>(p.cfg, p, ws, s) || ...))
+    (void)(launch_row<I, CONV, GEGLU, OUTF32, BUF>(gemm_default_tile(kTileStatic, GEGLU), p, ws, s) || ...);
 }
 
 template <int CONV, bool BUF>
 void launch_tiles(const GemmArgs& p, float* ws, hipStream_t s) {
-  if (p.act == ACT_GEGLU || p.act == ACT_SWIGLU) {
-    if constexpr (BUF) {
-      if (p.cfg == 12) return launch_t<128, 128, 2, 2, CONV, true, false, 4, true>(p, ws, s);
-    }
-    if (p.cfg == 6) launch_st<256, 128, 4, 2, CONV, true, false, BUF>(p, ws, s);
-    else launch_st<128, 128, 2, 2, CONV, true, false, BUF>(p, ws, s);
-  }
-  else if (p.out_f32) launch_cfg<CONV, true, BUF>(p, ws, s);
-  else launch_cfg<CONV, false, BUF>(p, ws, s);
+  if (p.act == ACT_GEGLU || p.act == ACT_SWIGLU) launch_cfg<CONV, true, false, BUF>(p, ws, s, GemmTileRows{});
+  else if (p.out_f32) launch_cfg<CONV, false, true, BUF>(p, ws, s, GemmTileRows{});
+  else launch_cfg<CONV, false, false, BUF>(p, ws, s, GemmTileRows{});
 }
 
 }  // namespace

@@ -559,26 +559,29 @@ void launch_pp(const GemmArgs& p, float* ws, hipStream_t s) {
   if (split > 1) launch_splitk_reduce<false>(p, ws, split, s);
 }
 
-// ping-pong tile menu (gemm.hip kPP* configs)
+// the ping-pong rows of the tile menu (gemm_tiles.h; a gated call takes the rows with a gated wave
+// layout); a config without an instantiation lands on the family's default tile
+template <int I, int CONV, bool GEGLU>
+bool launch_pp_row(int cfg, const GemmArgs& p, float* ws, hipStream_t s) {
+  constexpr GemmTile t = kGemmTiles[I];
+  if constexpr (t.family == kTilePingPong && (!GEGLU || t.gated())) {
+    if (t.id != cfg) return false;
+    launch_pp<t.BM, t.BN, GEGLU ? t.GWM : t.WM, GEGLU ? t.GWN : t.WN, CONV, GEGLU>(p, ws, s);
+    return true;
+  }
+  return false;
+}
+
+template <int CONV, bool GEGLU, int... I>
+void launch_pp_menu(const GemmArgs& p, float* ws, hipStream_t s, std::integer_sequence<int, I...>) {
+  if (!(launch_pp_row<I, CONV, GEGLU>(p.cfg, p, ws, s) || ...))
+    (void)(launch_pp_row<I, CONV, GEGLU>(gemm_default_tile(kTilePingPong, GEGLU), p, ws, s) || ...);
+}
+
 template <int CONV>
 void launch_pp_cfg(const GemmArgs& p, float* ws, hipStream_t s) {
-  if (is_gated(p.act)) {
-    // (256x256 gated spills: 256 VGPRs).  cfg 8: 256 x 160 with the 8 waves stacked along M
-    // (wave tile 32 x 160: 5 value/gate pairs), 80 outputs per block -- at M = 2048 x 5120 that
-    // is 512 blocks = 2 full rounds instead of 640 = 2.5 rounds of the 64-output 256 x 128 tile
-    if (p.cfg == 8) launch_pp<256, 160, 8, 1, CONV, true>(p, ws, s);
-    else launch_pp<256, 128, 4, 2, CONV, true>(p, ws, s);
-    return;
-  }
-  switch (p.cfg) {
-    case 8: launch_pp<256, 160, 4, 2, CONV, false>(p, ws, s); break;
-    case 9: launch_pp<256, 128, 4, 2, CONV, false>(p, ws, s); break;
-    case 10: launch_pp<128, 256, 2, 4, CONV, false>(p, ws, s); break;
-    case 20: launch_pp<128, 160, 4, 2, CONV, false>(p, ws, s); break;
-    case 21: launch_pp<128, 128, 4, 2, CONV, false>(p, ws, s); break;
-    case 22: launch_pp<128, 64, 4, 2, CONV, false>(p, ws, s); break;
-    default: launch_pp<256, 256, 4, 2, CONV, false>(p, ws, s); break;
-  }
+  if (is_gated(p.act)) launch_pp_menu<CONV, true>(p, ws, s, GemmTileRows{});
+  else launch_pp_menu<CONV, false>(p, ws, s, GemmTileRows{});
 }
 
 }  // namespace

@@ -566,6 +566,22 @@ def force_cfg():
     ext().gemm_set_override(-1, 0)
 
 
+@pytest.mark.parametrize("cfg", [0, 1, 2, 3, 4, 5, 6])
+def test_gemm_static_tiles_forced(cfg, force_cfg):
+    """every static tile forced once (the cost model alone never picks 5 / 6); the N <= 16 tile
+    takes only such shapes, so it gets N = 16.  Partial M and N tiles, 2 k-tiles."""
+    from cassmantle_amd.ops._ext import ext
+    M, N, K = 300, (16 if cfg == 4 else 200), 128
+    x = rnd(M, K, seed=141)
+    w = rnd(N, K, scale=K ** -0.5, seed=142)
+    b = rnd(N, scale=0.1, seed=143)
+    r = rnd(M, N, seed=144)
+    force_cfg(cfg, 1)
+    out = ops.linear(x, w, b, residual=r, act="silu")
+    assert tuple(ext().gemm_last_plan()) == (cfg, 1)
+    assert rel_err(out, ref.linear(x, w, b, residual=r, act="silu")) < 1e-2
+
+
 @pytest.mark.parametrize("cfg", PP_CFGS)
 @pytest.mark.parametrize("M,N,K,split", [(1000, 320, 320, 1), (4096, 640, 1280, 1), (300, 1280, 2560, 4),
                                          (77, 768, 768, 1), (2048, 200, 640, 2)])

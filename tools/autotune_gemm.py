@@ -26,10 +26,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cassmantle_amd import ops  # noqa: E402
 from cassmantle_amd.ops._ext import ext  # noqa: E402
 
-# the live tile configs (gemm.hip is_live_cfg): 0-10 4/8-wave and ping-pong tiles, 12-14 deep ring,
-# 15 = A-in-registers short-K kernel, 16 = 128x80 deep ring, 20-22 = pp 128x160 / 128x128 / 128x64,
-# 26/27 = 8-wave 128x80 / 128x64 deep ring, 31-33 = producer-wave 128x80 / 128x64 / 128x160 deep rings
-CFGS = [*range(0, 11), 12, 13, 14, 15, 16, 20, 21, 22, 26, 27, 31, 32, 33]
 SPLITS = [1, 2, 3, 4, 6, 8, 12, 16]
 
 
@@ -111,7 +107,8 @@ def main():
                          "copies totalling MIB MiB, e.g. 512 = twice the Infinity Cache), as in a "
                          "UNet eval; 0 = warm (the same weight tensor re-run)")
     a = ap.parse_args()
-    cfgs = [int(c) for c in a.cfgs.split(",")] if a.cfgs else CFGS
+    # default: the live tile configs (ops/csrc/gemm_tiles.h)
+    cfgs = [int(c) for c in a.cfgs.split(",")] if a.cfgs else [row[0] for row in ext().gemm_tile_menu()]
     os.environ["CASSMANTLE_GEMM_TUNE"] = "0"
     ops.set_mode("hip")
     ext().gemm_tune_clear()
