@@ -134,6 +134,17 @@ class ModelConfig:
     # whether a front-end still holds the device image or decodes the stored JPEG (the reference
     # blurs the decoded JPEG, src/server.py:53-56).  Needs gpu_jpeg and gpu_blur
     gpu_jpeg_content: bool = False
+    # a stored content JPEG with no device-resident source (a front-end restarted from a snapshot,
+    # another process, an older version) is decoded on the GPU too (ops.jpeg_decode, HIP: PIL's
+    # pixels bit for bit) instead of PIL on the host + an upload of the full-resolution pixels.
+    # A stream the decoder refuses, or one with fewer than jpeg_decode_min_intervals restart
+    # intervals (the entropy decoder's unit of parallel work), is left to PIL.  Needs gpu_blur.
+    # Off: today's path
+    gpu_jpeg_decode: bool = False
+    # 64: the smallest measured interval count at which the device path was no slower than PIL +
+    # upload in both repetitions at 512^2 and 1024^2 (profiles/jpeg_decode.jsonl; at 32 it ties,
+    # and a stream without restart markers, one lane for the whole image, is 13x slower)
+    jpeg_decode_min_intervals: int = 64
     # the GPU blur itself: gaussian (a true fp32 Gaussian, ops.gaussian_blur) | pil (Pillow's
     # GaussianBlur = three integer box passes per axis, bit for bit: ops.gaussian_blur_pil).  With
     # pil the masked pixels are those blur_pil gives on a CPU front-end and those of the reference

@@ -65,9 +65,13 @@ class BlurCache:
     """LRU of blurred JPEGs keyed by (content version, radius bucket)."""
 
     def __init__(self, blur_fn: Optional[BlurFn] = None, bucket: float = 0.25,
-                 quality: int = 75, capacity: int = 256, blur_jpeg_fn: Optional[BlurJpegFn] = None) -> None:
+                 quality: int = 75, capacity: int = 256, blur_jpeg_fn: Optional[BlurJpegFn] = None,
+                 decode_fn: Optional[Callable[[bytes], object]] = None) -> None:
         self.blur_fn = blur_fn or blur_pil
         self.blur_jpeg_fn = blur_jpeg_fn
+        # jpeg bytes -> their decoded pixels in HBM (runtime.factory.build_jpeg_decode_fn), or None
+        # for a stream it leaves to decode_jpeg; None: decode_jpeg (PIL on the host) always
+        self.decode_fn = decode_fn
         self.bucket = bucket
         self.quality = quality
         self.capacity = capacity
@@ -126,7 +130,9 @@ class BlurCache:
         if arr is None:
             ver, arr = self._decoded
             if ver != version:
-                arr = decode_jpeg(jpeg)
+                arr = self.decode_fn(jpeg) if self.decode_fn is not None else None
+                if arr is None:
+                    arr = decode_jpeg(jpeg)
                 self._decoded = (version, arr)
         return arr
 

@@ -54,7 +54,7 @@ class GameRoom:
                  image_gen: Optional[ImageGenerator] = None,
                  room_id: str = "", clock: Optional[Clock] = None,
                  rng: Optional[random.Random] = None,
-                 blur_fn=None, blur_jpeg_fn=None, content_jpeg_fn=None) -> None:
+                 blur_fn=None, blur_jpeg_fn=None, content_jpeg_fn=None, decode_fn=None) -> None:
         self.cfg = cfg
         self.store = store
         self.scorer = scorer
@@ -66,7 +66,7 @@ class GameRoom:
         self.seeds = load_seeds()          # src/backend.py:31-34
         self.styles = load_styles()        # src/backend.py:36-39
         self.blur_cache = BlurCache(blur_fn=blur_fn, bucket=cfg.blur_bucket, quality=cfg.jpeg_quality,
-                                    blur_jpeg_fn=blur_jpeg_fn)
+                                    blur_jpeg_fn=blur_jpeg_fn, decode_fn=decode_fn)
         # (DeviceImage, quality) -> (JPEG bytes, DeviceImage of their decoded pixels), both made on
         # the GPU (runtime.factory.build_content_jpeg_fn); None: PIL on the host
         self.content_jpeg_fn = content_jpeg_fn

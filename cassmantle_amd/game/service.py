@@ -33,7 +33,7 @@ class GameService:
                  prompt_gen: Optional[PromptGenerator] = None,
                  clock: Optional[Clock] = None, store: Optional[StateStore] = None,
                  room_ids: Optional[List[str]] = None, seed: Optional[int] = None,
-                 blur_fn=None, blur_jpeg_fn=None, content_jpeg_fn=None) -> None:
+                 blur_fn=None, blur_jpeg_fn=None, content_jpeg_fn=None, decode_fn=None) -> None:
         self.cfg = cfg
         self.clock = clock or Clock()
         self.store = store or StateStore(self.clock)
@@ -47,7 +47,8 @@ class GameService:
                                        prompt_gen=prompt_gen or SyntheticPromptGenerator(salt=hash(rid) & 0xffff),
                                        image_gen=gen_for(rid), room_id=rid, clock=self.clock,
                                        rng=random.Random(rng.random()), blur_fn=blur_fn,
-                                       blur_jpeg_fn=blur_jpeg_fn, content_jpeg_fn=content_jpeg_fn)
+                                       blur_jpeg_fn=blur_jpeg_fn, content_jpeg_fn=content_jpeg_fn,
+                                       decode_fn=decode_fn)
         self._tasks: List[asyncio.Task] = []
         self._stop: Optional[asyncio.Event] = None
         if cfg.game.snapshot_path:

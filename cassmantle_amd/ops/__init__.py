@@ -894,6 +894,116 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
     return outs, decoded
 
 
+_JPEG_DECODE_PLANS: dict = {}     # (device, header key) -> the stream's tables on the device
+
+
+def _jpeg_decode_plan(device, stream):
+    """The constant inputs of a decode on ``device``, uploaded once per identical header: int32
+    [672 + 1024] = the stream's quantisation tables as jpeg_reconstruct reads them (natural order;
+    the Huffman words behind them are not read) | the same tables in zig-zag order | the four
+    decode tables of the stream's DHT."""
+    from . import jpeg_format as jf
+    key = (device, stream.header_key)
+    plan = _JPEG_DECODE_PLANS.get(key)
+    if plan is None:
+        import numpy as np
+        lq, cq = stream.qtables
+        tables = np.zeros(128 + 544 + 128 + 4 * jf.DEC_TABLE_WORDS, dtype=np.int32)
+        tables[:128] = lq + cq
+        tables[672: 672 + 128] = [t[jf.ZIGZAG[z]] for t in (lq, cq) for z in range(64)]
+        tables[672 + 128:] = jf.decode_tables(stream.huff)
+        if len(_JPEG_DECODE_PLANS) >= 64:
+            _JPEG_DECODE_PLANS.clear()
+        plan = _JPEG_DECODE_PLANS[key] = torch.from_numpy(tables).to(device)
+    return plan
+
+
+def _jpeg_decode_inputs(streams, device):
+    """The device inputs of one decode of parsed ``streams`` (one header key): the staged uint8
+    buffer (interval table, then every stream's entropy-coded segment, scan start .. EOI) after its
+    one non-blocking copy from pinned memory, the number of bytes behind the table, the tables."""
+    import numpy as np
+    s0 = streams[0]
+    B, nint = len(streams), len(s0.intervals)
+    ivals = np.empty((B, nint, 2), dtype=np.uint32)
+    segs, base = [], 0
+    for i, s in enumerate(streams):
+        iv = np.asarray(s.intervals, dtype=np.int64)
+        end = int(iv[-1, 0] + iv[-1, 1])
+        ivals[i, :, 0] = iv[:, 0] - s.scan_offset + base
+        ivals[i, :, 1] = iv[:, 1]
+        segs.append(memoryview(s.data)[s.scan_offset: end])
+        base += end - s.scan_offset
+    if base >= 2 ** 32 - 1:
+        raise ValueError("jpeg_decode: batch too large for 32-bit byte offsets")
+    nstage = (8 * B * nint + base + 15) // 16 * 16           # padded: word reads stay inside
+    stage = torch.empty(nstage, dtype=torch.uint8, pin_memory=True)
+    host = stage.numpy()
+    host[: 8 * B * nint] = ivals.reshape(-1).view(np.uint8)
+    p = 8 * B * nint
+    for seg in segs:
+        host[p: p + len(seg)] = np.frombuffer(seg, dtype=np.uint8)
+        p += len(seg)
+    host[p:] = 0
+    return stage.to(device, non_blocking=True), base, _jpeg_decode_plan(device, s0)
+
+
+def jpeg_decode(data, device=None, out=None):
+    """Baseline JPEG bytes -> uint8 ``[H, W, 3]`` on ``device``: the pixels a libjpeg decoder (PIL)
+    returns for them, bit for bit ``ops.reference.jpeg_decode`` (the entropy decode and decode
+    contracts: ops/csrc/jpeg.hip).  ``data``: ``bytes`` (or a parsed ``jpeg_format.JpegStream``), or
+    a list of streams with identical geometry and tables -> ``[B, H, W, 3]``; anything else in one
+    call is a ``ValueError``.  ``out``: a contiguous uint8 buffer of that shape on ``device``.
+    ``jpeg_format.JpegUnsupported`` for a stream outside the decoder's scope (baseline, 8 bit,
+    4:2:0 or 4:4:4, one scan) or one the refusal rule turns away, ``jpeg_format.JpegError`` for
+    malformed bytes (both ``ValueError``; ``.code`` and ``.interval`` say what and where).
+
+    HIP path, all on the current stream: the header parse and the marker scan on the host, one
+    pinned staging buffer and one host-to-device copy of the interval table and the entropy-coded
+    bytes (the tables are uploaded once per identical header), zero + entropy decode (one lane per
+    restart interval), inverse DCT + colour, and one 8-byte device-to-host copy of the status
+    word: the only synchronisation."""
+    from . import jpeg_format as jf
+    import numpy as np
+    single = isinstance(data, (bytes, bytearray, memoryview, jf.JpegStream))
+    items = [data] if single else list(data)
+    if not items:
+        raise ValueError("jpeg_decode: no stream")
+    streams = [d if isinstance(d, jf.JpegStream) else jf.parse(d) for d in items]
+    s0 = streams[0]
+    if any(s.header_key != s0.header_key for s in streams[1:]):
+        raise ValueError("jpeg_decode: the streams of one call must share geometry, tables and restart interval")
+    B, H, W = len(streams), s0.H, s0.W
+    dev = torch.device(device if device is not None else (out.device if out is not None else "cpu"))
+    if out is not None:
+        want = (H, W, 3) if single else (B, H, W, 3)
+        if (tuple(out.shape) != want or out.dtype != torch.uint8 or out.device.type != dev.type
+                or not out.is_contiguous()):
+            raise ValueError(f"jpeg_decode: out must be a contiguous uint8 {list(want)} buffer on the device")
+        dev = out.device
+    probe = out if out is not None else torch.empty(0, device=dev)
+    if not _use_hip(probe):
+        px = np.stack([jf.reconstruct(jf.entropy_decode(s, i * len(s.intervals)), H, W, 0, s.sampling,
+                                      tables=s.qtables) for i, s in enumerate(streams)])
+        res = torch.from_numpy(px[0] if single else px).to(dev)
+        return res if out is None else out.copy_(res)
+    _, nb, mx, my = jf.geometry(H, W, s0.sampling)
+    staged, base, tables = _jpeg_decode_inputs(streams, probe.device)
+    ncoef = B * mx * my * nb * 64
+    buf = torch.empty(ncoef + 8, device=probe.device, dtype=torch.int16)
+    s420 = int(s0.sampling == "420")
+    ext().jpeg_entropy_decode(staged, base, tables, buf, B, H, W, s420, s0.restart)
+    planes = torch.empty(ncoef, device=probe.device, dtype=torch.uint8)
+    res = out if out is not None else torch.empty((H, W, 3) if single else (B, H, W, 3),
+                                                  device=probe.device, dtype=torch.uint8)
+    ext().jpeg_reconstruct(buf[:ncoef].view(B, mx * my, nb, 64), tables[:672], planes, res.view(B, H, W, 3),
+                           H, W, s420)
+    status = int(buf[ncoef: ncoef + 4].view(torch.int64).cpu().item()) & (2 ** 64 - 1)      # the only sync
+    if status:
+        jf.raise_status(status & 0xFFFFFFFF, 0xFFFFFFFF - (status >> 32))
+    return res
+
+
 def vae_postprocess(x: torch.Tensor) -> torch.Tensor:
     """[B,H,W,3] in [-1,1] -> uint8 [B,H,W,3] (clamp((x+1)/2)*255, round)."""
     if not _use_hip(x):

@@ -944,6 +944,45 @@ void jpeg_reconstruct(const at::Tensor& coef, const at::Tensor& tables, at::Tens
   launch_jpeg_reconstruct(a, cur_stream());
 }
 
+// Entropy decode of B baseline streams of one geometry (entropy decode contract: jpeg.hip).
+// staged uint8 = the interval table (uint32 [B * intervals][2]: offset, length) followed by the
+// nbytes bytes the offsets index; tables int32 [672 + 1024] = the quantisation tables as
+// jpeg_reconstruct reads them (natural order, 128 of the 672 words used) | zig-zag quantisation
+// tables | four decode tables; buf int16 [B * mcus * blocks * 64 + 8]: the coefficients, then the
+// 64-bit status word (and 8 bytes of padding), all zeroed here.  restart 0: one interval.
+void jpeg_entropy_decode(const at::Tensor& staged, int64_t nbytes, const at::Tensor& tables, at::Tensor& buf,
+                         int64_t B, int64_t H, int64_t W, int64_t s420, int64_t restart) {
+  CHECK_DEV(staged); CHECK_CONTIG(staged); CHECK_DEV(tables); CHECK_CONTIG(tables); CHECK_DEV(buf); CHECK_CONTIG(buf);
+  TORCH_CHECK(B > 0 && H > 0 && W > 0 && H < 65536 && W < 65536, "jpeg: image sides must be in 1..65535");
+  TORCH_CHECK(restart >= 0 && restart < 65536, "jpeg: restart interval 0..65535");
+  TORCH_CHECK(tables.scalar_type() == at::kInt && tables.numel() == 128 + 544 + 1024,
+              "jpeg: decode tables int32 [672 + 1024]");
+  JpegArgs a;
+  a.B = (int)B; a.H = (int)H; a.W = (int)W;
+  const int mcu = s420 ? 16 : 8;
+  a.nb = s420 ? 6 : 3;
+  a.mx = (a.W + mcu - 1) / mcu; a.my = (a.H + mcu - 1) / mcu;
+  const long long mcus = (long long)a.mx * a.my;
+  a.restart = restart ? (int)restart : (int)mcus;
+  a.nint = (int)((mcus + a.restart - 1) / a.restart);
+  const long long nivals = B * a.nint, ncoef = B * mcus * a.nb * 64;
+  TORCH_CHECK(nivals < 2147483647LL, "jpeg: too many restart intervals for one launch");
+  TORCH_CHECK(buf.scalar_type() == at::kShort && buf.numel() == ncoef + 8, "jpeg: buf int16 [B * mcus * blocks * 64 + 8]");
+  TORCH_CHECK(nbytes >= 0 && nbytes < 4294967295LL && staged.scalar_type() == at::kByte &&
+              staged.numel() >= 8 * nivals + nbytes, "jpeg: staged uint8 [8 * B * intervals + nbytes]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(staged.data_ptr()) % 4 == 0 && reinterpret_cast<uintptr_t>(buf.data_ptr()) % 16 == 0,
+              "jpeg: staged 4-byte aligned, buf 16-byte aligned");
+  a.coef = buf.data_ptr<int16_t>();
+  JpegDecodeIn d;
+  d.intervals = reinterpret_cast<const uint32_t*>(staged.data_ptr<uint8_t>());
+  d.bytes = staged.data_ptr<uint8_t>() + 8 * nivals;
+  d.nbytes = (uint32_t)nbytes;
+  d.tables = reinterpret_cast<const uint32_t*>(tables.data_ptr<int>()) + 128 + 544;
+  d.status = reinterpret_cast<unsigned long long*>(a.coef + ncoef);     // 8-byte aligned: ncoef is a multiple of 64
+  d.zero_bytes = (ncoef + 8) * 2;
+  launch_jpeg_entropy_decode(a, d, cur_stream());
+}
+
 // PIL's GaussianBlur (blur contract: blur_pil.hip).  img uint8 [H, W, 3]; out uint8 [N, H, W, 3].
 void blur_pil_check(const at::Tensor& img, const at::Tensor& out) {
   CHECK_DEV(img); CHECK_CONTIG(img); CHECK_DEV(out); CHECK_CONTIG(out);
@@ -1051,6 +1090,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("jpeg_count", &jpeg_count, nogil());
   m.def("jpeg_write", &jpeg_write, nogil());
   m.def("jpeg_reconstruct", &jpeg_reconstruct, nogil());
+  m.def("jpeg_entropy_decode", &jpeg_entropy_decode, nogil());
   m.def("timestep_embedding", &timestep_embedding, nogil());
   m.def("gather_add", &gather_add, nogil());
   m.def("concat2", &concat2, nogil());

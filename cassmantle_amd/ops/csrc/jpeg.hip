@@ -73,8 +73,49 @@
 //
 // Kernels: idct (one wave per MCU, the mirror of transform; uint8 samples into padded planes) ->
 // colour (upsampling crosses block and MCU borders, so it reads the planes: 4 pixels per lane).
+//
+// THE ENTROPY DECODE CONTRACT (jpeg_format.entropy_decode is its numpy reference, jpeg_entropy_dec.h
+// the routine): the bytes of one restart interval of any baseline scan in scope (SOF0, 8-bit,
+// 4:2:0 or 4:4:4, one interleaved scan, the stream's own DQT / DHT; jpeg_format.parse) -> the
+// quantised zig-zag coefficients the DECODE CONTRACT starts from.  The host finds the intervals
+// (in entropy-coded data every 0xFF is followed by 0x00 or by a marker), so an interval is the
+// bytes between two markers, markers excluded.
+//
+//   Bit order.  Bytes in stream order, bits of a byte MSB first; a code word and the value bits
+//   after it are read in that order.
+//   Unstuffing.  0xFF 0x00 is the data byte 0xFF.  A 0xFF followed by anything else, or ending the
+//   interval, ends the data there.  Bits left after the last block (the padding) are ignored.
+//   Canonical codes (T.81 Annex C).  For a DHT (BITS[1..16], HUFFVAL): code = 0; for l = 1..16 the
+//   next BITS[l] values get the codes code, code + 1, ... of length l; then code <<= 1.  The
+//   symbol is that of the shortest l whose first l bits are such a code.
+//   EXTEND.  A symbol's size s is followed by s bits u (MSB first): v = u if u >= 2^(s-1), else
+//   v = u - 2^s + 1.  s = 0 has no bits and v = 0.
+//   Block.  DC symbol = s (<= 11): coefficient 0 = predictor + v, which becomes the predictor of
+//   its component.  Then from k = 1, AC symbol (run << 4) | s: 0x00 (EOB) ends the block, the
+//   rest is zero; 0xF0 (ZRL) is k += 16; otherwise (1 <= s <= 10) k += run, coefficient k = v,
+//   k += 1.  The block also ends after k = 63.  Luma blocks use the tables the first component
+//   names, chroma blocks the other two components' (shared) tables.
+//   DC prediction.  The three predictors start at 0 in every interval.  Interval i holds the MCUs
+//   i * restart .. min((i + 1) * restart, mcus) - 1 in raster order (no DRI: all of them).
+//   Errors, the first in decode order being the interval's status:
+//     TRUNCATED (1)  a code word or value bits are wanted beyond the end of the data
+//     BAD_CODE  (2)  16 bits that start no code word; a DC size above 11; an AC size above 10; an
+//                    AC symbol with s = 0 other than EOB and ZRL
+//     OVERRUN   (3)  k beyond 63 after a run, or after a ZRL (no coefficient can follow it)
+//     WIDE      (4)  the refusal rule: with d = coefficient * Q, a block with any |d| > T or
+//                    sum d^2 > T^2, T = 2047 (jpeg_format.WIDE_T: the 32-bit words of the idct
+//                    kernel and the 16-bit words of libjpeg's SIMD inverse DCT hold everything
+//                    below it, and no block of 8-bit samples reaches it)
+//   An interval with an error is abandoned; the status of a call is the error of its lowest
+//   interval (image * intervals + interval), and then no pixels are returned: a refusal, never
+//   different pixels.
+//
+// Kernel: entropy decode, one lane per restart interval like the coder it mirrors, the decode
+// tables (about 4 KiB) in LDS; the coefficient buffer is zeroed first and only non-zero
+// coefficients are stored.
 #include "common.h"
 #include "kernels.h"
+#include "jpeg_entropy_dec.h"
 
 namespace {
 
@@ -530,6 +571,34 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(JpegArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------- entropy decode
+// one lane per restart interval (gid = image * nint + interval), the mirror of jpeg_entropy_kernel.
+// Lanes diverge by design (every interval is its own bit stream); the per-lane state is the bit
+// window, three predictors and a few scalars, no indexed register arrays.
+__global__ __launch_bounds__(64) void jpeg_entropy_decode_kernel(JpegArgs a, JpegDecodeIn d) {
+  __shared__ uint32_t tabs[JPEG_DEC_WORDS];
+  for (int i = threadIdx.x; i < JPEG_DEC_WORDS; i += 64) tabs[i] = d.tables[i];
+  __syncthreads();
+  const long long gid = (long long)blockIdx.x * 64 + threadIdx.x;
+  if (gid >= (long long)a.B * a.nint) return;
+  const int b = (int)(gid / a.nint), it = (int)(gid % a.nint);
+  const int mcus = a.mx * a.my;
+  const int m0 = it * a.restart;
+  const uint32_t off = d.intervals[2 * gid], len = d.intervals[2 * gid + 1];
+  int st;
+  if (m0 >= mcus) {
+    st = JPEG_DEC_OVERRUN;
+  } else if (off > d.nbytes || len > d.nbytes - off) {
+    st = JPEG_DEC_TRUNCATED;
+  } else {
+    st = jpeg_decode_interval(d.bytes + off, len, tabs, a.nb, min(a.restart, mcus - m0),
+                              a.coef + ((long long)b * mcus + m0) * a.nb * 64);
+  }
+  // the error of the lowest gid wins: larger key = smaller gid; 0 = every interval OK
+  if (st != JPEG_DEC_OK)
+    atomicMax(d.status, ((unsigned long long)(0xffffffffu - (uint32_t)gid) << 32) | (unsigned long long)st);
+}
+
 }  // namespace
 
 void launch_jpeg_count(const JpegArgs& a, hipStream_t s) {
@@ -560,4 +629,10 @@ void launch_jpeg_reconstruct(const JpegArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(jpeg_idct_kernel<false>, dim3(ig), dim3(64 * TR_WAVES), 0, s, a);
     hipLaunchKernelGGL(jpeg_colour_kernel<false>, dim3(cg), dim3(256), 0, s, a);
   }
+}
+
+void launch_jpeg_entropy_decode(const JpegArgs& a, const JpegDecodeIn& d, hipStream_t s) {
+  launch_zero(a.coef, d.zero_bytes, s);
+  const unsigned eg = (unsigned)(((long long)a.B * a.nint + 63) / 64);
+  hipLaunchKernelGGL(jpeg_entropy_decode_kernel, dim3(eg), dim3(64), 0, s, a, d);
 }

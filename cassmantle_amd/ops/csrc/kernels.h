@@ -238,6 +238,18 @@ void launch_jpeg_write(const JpegArgs& a, hipStream_t s);
 // inverse DCT of coef into planes, then upsampling + colour into dec (reads B, H, W, nb, mx, my,
 // qtab, coef only)
 void launch_jpeg_reconstruct(const JpegArgs& a, hipStream_t s);
+// entropy decode (entropy decode contract in jpeg.hip's header comment; jpeg_entropy_dec.h)
+struct JpegDecodeIn {
+  const uint8_t* bytes = nullptr;        // the entropy-coded data of the batch
+  uint32_t nbytes = 0;                   // every interval is checked to lie in bytes[0 .. nbytes)
+  const uint32_t* intervals = nullptr;   // [B][nint] (offset into bytes, length), markers excluded
+  const uint32_t* tables = nullptr;      // [JPEG_DEC_WORDS] zig-zag quantisation tables | four decode tables
+  unsigned long long* status = nullptr;  // 0: every interval OK, else (0xffffffff - gid) << 32 | status of the lowest gid
+  long long zero_bytes = 0;              // from a.coef: the coefficients and the status word behind them
+};
+// zeroes coef and status, then one lane per interval: fills coef (reads B, nb, mx, my, restart,
+// nint, coef of a; restart = MCUs per interval, all of them without DRI)
+void launch_jpeg_entropy_decode(const JpegArgs& a, const JpegDecodeIn& d, hipStream_t s);
 
 // PIL's GaussianBlur, bit for bit (blur_pil.hip; blur contract in its header comment)
 int blur_pil_max_tiled_radius();

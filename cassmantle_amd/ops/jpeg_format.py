@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import struct
 from functools import lru_cache
+from dataclasses import dataclass
 from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
@@ -358,11 +359,13 @@ def _upsample_h2v2(c: np.ndarray, see) -> np.ndarray:
     return see(3 * s[:, x >> 1] + s[:, side] + np.where(x & 1, 7, 8)) >> 4
 
 
-def reconstruct(coef: np.ndarray, H: int, W: int, quality: int, sampling: str, stats: dict = None) -> np.ndarray:
+def reconstruct(coef: np.ndarray, H: int, W: int, quality: int, sampling: str, stats: dict = None,
+                tables=None) -> np.ndarray:
     """int16 [mcus, blocks per MCU, 64] quantised zig-zag coefficients (:func:`coefficients`) ->
     uint8 [H, W, 3], the pixels a libjpeg decoder gives for the JPEG of those coefficients.
     Computed in int64; ``stats["max_abs"]`` receives the largest magnitude of any intermediate
-    (the kernel works in 32-bit words)."""
+    (the kernel works in 32-bit words).  ``tables``: ``(luma, chroma)`` quantisation tables in
+    natural order, used in place of ``quant_tables(quality)`` (a foreign stream's DQT)."""
     _, nb, mx, my = geometry(H, W, sampling)
     peak = [0]
 
@@ -370,7 +373,7 @@ def reconstruct(coef: np.ndarray, H: int, W: int, quality: int, sampling: str, s
         peak[0] = max(peak[0], int(np.abs(v).max()))
         return v
 
-    lq, cq = quant_tables(quality)
+    lq, cq = quant_tables(quality) if tables is None else tables
     q = np.empty((nb, 64), dtype=np.int64)
     q[:nb - 2], q[nb - 2:] = np.asarray(lq), np.asarray(cq)
     nat = np.empty(coef.shape, dtype=np.int64)
@@ -402,3 +405,439 @@ def jpeg_decoded(images, quality: int = 75, sampling: str = "420") -> np.ndarray
     _, H, W, _ = arr.shape
     return np.stack([reconstruct(coefficients(img, int(quality), sampling), H, W, int(quality), sampling)
                      for img in arr])
+
+
+# ----------------------------------------------------------------------------- entropy decode contract
+# Bytes -> quantised coefficients: the mirror of :func:`entropy` for any baseline stream in scope
+# (its own DQT / DHT).  Formulas: the ENTROPY DECODE CONTRACT section of jpeg.hip's header comment;
+# ops/csrc/jpeg_entropy_dec.h is the per-interval routine the kernel and the host program compile.
+class JpegError(ValueError):
+    """Malformed JPEG bytes.  ``code`` is a status of the entropy decode contract (0 for a fault the
+    header parse found), ``interval`` the restart interval (image * intervals + index) it is in."""
+
+    def __init__(self, msg: str, code: int = 0, interval: int = -1) -> None:
+        super().__init__(msg)
+        self.code, self.interval = code, interval
+
+
+class JpegUnsupported(ValueError):
+    """A JPEG outside the decoder's scope (or a block the 32-bit arithmetic refuses: WIDE)."""
+
+    def __init__(self, msg: str, code: int = 0, interval: int = -1) -> None:
+        super().__init__(msg)
+        self.code, self.interval = code, interval
+
+
+OK, TRUNCATED, BAD_CODE, OVERRUN, WIDE = 0, 1, 2, 3, 4
+STATUS_NAMES = ("OK", "TRUNCATED", "BAD_CODE", "OVERRUN", "WIDE")
+# The refusal rule: a block whose dequantised coefficients d have sum d^2 > WIDE_T^2 is refused.
+# Two bounds meet in WIDE_T.  (1) The 32-bit inverse DCT: every intermediate is at most
+# idct_gain()[0] * ||d||_2 (+ the rounding carried between the passes), below 2^31 up to
+# ||d||_2 = 6392.  (2) The decoder the pixels are defined by: libjpeg-turbo's SIMD inverse DCT
+# keeps the first pass's outputs, and sums of two of them, in 16-bit words.  A first-pass output
+# is at most 4 sqrt(8) times the norm of its coefficient column, a sum of two at most
+# 16 ||d||_2, so ||d||_2 <= 2047 keeps them below 2^15; measured, crafted blocks agree with PIL
+# up to 2047 and stop agreeing at 2100 (tests/test_jpeg_entropy_decode.py).  A block of 8-bit
+# samples has at most 1024 (Parseval) + 1020 (half the norm of an all-255 table) = 2044.
+WIDE_T = 2047
+DEC_LOOK_BITS = 8
+DEC_TABLE_WORDS = 128 + 16 + 16 + 64      # per Huffman table: look-ahead | limits | value offsets | values
+
+
+def raise_status(code: int, interval: int):
+    """The exception of a status word other than OK."""
+    name = STATUS_NAMES[code] if 0 < code < len(STATUS_NAMES) else f"status {code}"
+    if code == WIDE:
+        raise JpegUnsupported(f"jpeg: interval {interval}: a block's dequantised energy is over {WIDE_T}^2 (WIDE)",
+                              code, interval)
+    raise JpegError(f"jpeg: interval {interval}: {name}", code, interval)
+
+
+@lru_cache(maxsize=None)
+def idct_gain() -> Tuple[float, float]:
+    """(largest L2 gain from the 64 dequantised inputs of a block to any intermediate of the two
+    inverse DCT passes, largest L1 gain from the 8 inputs of one pass to any of its intermediates):
+    unit impulses through :func:`_idct_pass` in exact arithmetic.  |intermediate| <= L2 gain *
+    ||d||_2, plus the L1 gain times the rounding error (below 1) of the values between the passes."""
+    class Lin:                           # a linear form over the basis, integer coefficients
+        def __init__(self, v):
+            self.v = v
+        __add__ = lambda a, b: Lin(a.v + (b.v if isinstance(b, Lin) else 0))      # noqa: E731
+        __sub__ = lambda a, b: Lin(a.v - b.v)                                     # noqa: E731
+        __mul__ = lambda a, k: Lin(a.v * k)                                       # noqa: E731
+        __lshift__ = lambda a, k: Lin(a.v * (1 << k))                             # noqa: E731
+        __rshift__ = lambda a, k: Lin(a.v / float(1 << k))                        # noqa: E731
+    l2, l1 = [0.0], [0.0]
+
+    def see2(x):
+        l2[0] = max(l2[0], float(np.sqrt((x.v.astype(np.float64) ** 2).sum(0)).max()))
+        return x
+
+    def see1(x):
+        l1[0] = max(l1[0], float(np.abs(x.v).sum(0).max()))
+        return x
+    d = np.eye(64, dtype=np.float64).reshape(64, 8, 8)
+    ws = _idct_pass([Lin(d[:, k, :]) for k in range(8)], IDCT_BITS - IDCT_PASS1, see2)
+    w = np.stack([x.v for x in ws], axis=-2)
+    _idct_pass([Lin(w[..., k]) for k in range(8)], IDCT_BITS + IDCT_PASS1 + 3, see2)
+    _idct_pass([Lin(np.eye(8)[:, k]) for k in range(8)], 1, see1)
+    return l2[0], l1[0]
+
+
+@dataclass(frozen=True)
+class JpegStream:
+    """What :func:`parse` reads from a baseline JPEG: geometry, the stream's own tables and where
+    its restart intervals lie."""
+    data: bytes
+    H: int
+    W: int
+    sampling: str
+    qtables: Tuple[Tuple[int, ...], Tuple[int, ...]]       # luma, chroma, natural order
+    huff: Tuple[Tuple[Tuple[int, ...], Tuple[int, ...]], ...]      # (bits, values): DC luma, DC chroma, AC luma, AC chroma
+    restart: int                                           # MCUs per interval, 0: no DRI
+    scan_offset: int                                       # first byte of the entropy-coded segment
+    intervals: Tuple[Tuple[int, int], ...]                 # (offset, length) in data, markers excluded
+
+    @property
+    def header_key(self):
+        """Equal for streams one batched decode accepts: same geometry, tables, interval count."""
+        return (self.H, self.W, self.sampling, self.qtables, self.huff, self.restart, len(self.intervals))
+
+
+def _check_dht(bits: Sequence[int], vals: Sequence[int], ac: bool) -> None:
+    code = 0
+    for length in range(1, 17):
+        code += bits[length - 1]
+        if code > (1 << length):
+            raise JpegError("jpeg: DHT assigns more codes than a length has")
+        code <<= 1
+    if len(set(vals)) != len(vals):
+        raise JpegError("jpeg: DHT lists a symbol twice")
+    for v in vals:
+        if (v > 11) if not ac else ((v & 15) > 10 or ((v & 15) == 0 and v not in (0x00, 0xF0))):
+            raise JpegUnsupported(f"jpeg: Huffman symbol 0x{v:02x} is not a baseline 8-bit symbol")
+
+
+def parse(data) -> JpegStream:
+    """The header of a baseline JPEG in scope and the position of every restart interval.  Scope:
+    SOF0, 8-bit samples, 8-bit DQT, three components with sampling factors (2x2, 1x1, 1x1) or all
+    1x1, the two chroma components sharing their tables, one interleaved scan, no Adobe APP14
+    segment.  :class:`JpegUnsupported` outside it, :class:`JpegError` for malformed bytes."""
+    data = bytes(data)
+    n = len(data)
+    if n < 4 or data[:2] != b"\xff\xd8":
+        raise JpegError("jpeg: no SOI marker")
+    qt: Dict[int, Tuple[int, ...]] = {}
+    ht: Dict[Tuple[int, int], Tuple[Tuple[int, ...], Tuple[int, ...]]] = {}
+    frame = None
+    restart = 0
+    pos = 2
+    while True:
+        if pos + 4 > n:
+            raise JpegError("jpeg: the header ends before SOS")
+        if data[pos] != 0xFF:
+            raise JpegError(f"jpeg: marker expected at byte {pos}")
+        m = data[pos + 1]
+        if m == 0xFF:                    # fill byte
+            pos += 1
+            continue
+        if m in (0xD8, 0xD9, 0x01) or 0xD0 <= m <= 0xD7:
+            raise JpegError(f"jpeg: marker 0x{m:02x} in the header")
+        ln = (data[pos + 2] << 8) | data[pos + 3]
+        if ln < 2 or pos + 2 + ln > n:
+            raise JpegError(f"jpeg: segment 0x{m:02x} runs past the end")
+        seg = data[pos + 4: pos + 2 + ln]
+        pos += 2 + ln
+        if m == 0xDB:
+            k = 0
+            while k < len(seg):
+                pq, tq = seg[k] >> 4, seg[k] & 15
+                if pq != 0:
+                    raise JpegUnsupported("jpeg: 16-bit quantisation table")
+                if tq > 3 or k + 65 > len(seg):
+                    raise JpegError("jpeg: malformed DQT")
+                zz = seg[k + 1: k + 65]
+                if 0 in zz:
+                    raise JpegError("jpeg: zero in a quantisation table")
+                nat = [0] * 64
+                for z in range(64):
+                    nat[ZIGZAG[z]] = zz[z]
+                qt[tq] = tuple(nat)
+                k += 65
+        elif m == 0xC4:
+            k = 0
+            while k < len(seg):
+                if k + 17 > len(seg):
+                    raise JpegError("jpeg: malformed DHT")
+                tc, th = seg[k] >> 4, seg[k] & 15
+                bits = tuple(seg[k + 1: k + 17])
+                cnt = sum(bits)
+                if tc > 1 or th > 3 or cnt > 256 or k + 17 + cnt > len(seg):
+                    raise JpegError("jpeg: malformed DHT")
+                vals = tuple(seg[k + 17: k + 17 + cnt])
+                _check_dht(bits, vals, tc == 1)
+                ht[(tc, th)] = (bits, vals)
+                k += 17 + cnt
+        elif m == 0xC0:
+            if frame is not None:
+                raise JpegError("jpeg: two frame headers")
+            if len(seg) < 6:
+                raise JpegError("jpeg: malformed SOF0")
+            prec, H, W, nc = seg[0], (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
+            if prec != 8:
+                raise JpegUnsupported(f"jpeg: {prec}-bit samples")
+            if nc != 3:
+                raise JpegUnsupported(f"jpeg: {nc} components (three expected)")
+            if len(seg) != 6 + 3 * nc:
+                raise JpegError("jpeg: malformed SOF0")
+            if H == 0 or W == 0:
+                raise JpegUnsupported("jpeg: zero image side (DNL)")
+            comps = [(seg[6 + 3 * i], seg[7 + 3 * i], seg[8 + 3 * i]) for i in range(3)]
+            hv = tuple(c[1] for c in comps)
+            if hv == (0x22, 0x11, 0x11):
+                sampling = "420"
+            elif hv == (0x11, 0x11, 0x11):
+                sampling = "444"
+            else:
+                raise JpegUnsupported("jpeg: sampling factors other than 4:2:0 and 4:4:4")
+            frame = (H, W, sampling, comps)
+        elif 0xC1 <= m <= 0xCF and m != 0xC8:
+            raise JpegUnsupported(f"jpeg: frame type 0x{m:02x} (baseline SOF0 only)")
+        elif m == 0xDD:
+            if len(seg) != 2:
+                raise JpegError("jpeg: malformed DRI")
+            restart = (seg[0] << 8) | seg[1]
+        elif m == 0xEE and seg[:5] == b"Adobe":
+            raise JpegUnsupported("jpeg: Adobe APP14 segment (colour transform)")
+        elif m == 0xDC:
+            raise JpegUnsupported("jpeg: DNL")
+        elif m == 0xDA:
+            break
+    if frame is None:
+        raise JpegError("jpeg: SOS before SOF0")
+    H, W, sampling, comps = frame
+    if len(seg) < 1 or seg[0] != 3:
+        raise JpegUnsupported("jpeg: a scan that is not the three components interleaved")
+    if len(seg) != 10:
+        raise JpegError("jpeg: malformed SOS")
+    if tuple(seg[1 + 2 * i] for i in range(3)) != tuple(c[0] for c in comps):
+        raise JpegUnsupported("jpeg: scan components out of frame order")
+    if tuple(seg[7:10]) != (0, 63, 0):
+        raise JpegUnsupported("jpeg: spectral selection / successive approximation")
+    sel = [(seg[2 + 2 * i] >> 4, seg[2 + 2 * i] & 15) for i in range(3)]
+    if sel[1] != sel[2] or comps[1][2] != comps[2][2]:
+        raise JpegUnsupported("jpeg: the chroma components do not share their tables")
+    try:
+        qtables = (qt[comps[0][2]], qt[comps[1][2]])
+        huff = (ht[(0, sel[0][0])], ht[(0, sel[1][0])], ht[(1, sel[0][1])], ht[(1, sel[1][1])])
+    except KeyError:
+        raise JpegError("jpeg: the scan names a table the stream does not define") from None
+    # marker scan of the entropy-coded segment: every 0xFF there is followed by 0x00 or a marker
+    a = np.frombuffer(data, dtype=np.uint8)[pos:]
+    ff = np.flatnonzero(a[:-1] == 0xFF)
+    mk = ff[a[ff + 1] != 0]
+    codes = a[mk + 1]
+    end = np.flatnonzero(codes == 0xD9)
+    if end.size == 0:
+        raise JpegError("jpeg: no EOI marker")
+    k = int(end[0])
+    rst = codes[:k].astype(np.int64) - 0xD0
+    if k and (int(rst.min()) < 0 or int(rst.max()) > 7):
+        other = int(codes[:k][(rst < 0) | (rst > 7)][0])
+        if other == 0xFF:
+            raise JpegUnsupported("jpeg: fill bytes in the entropy-coded segment")
+        if other in (0xDA, 0xC4, 0xDB, 0xDD):
+            raise JpegUnsupported("jpeg: more than one scan")
+        raise JpegError(f"jpeg: marker 0x{other:02x} in the entropy-coded segment")
+    if k and not np.array_equal(rst, np.arange(k) & 7):
+        raise JpegError("jpeg: restart markers out of sequence")
+    _, _, mx, my = geometry(H, W, sampling)
+    want = (mx * my + restart - 1) // restart if restart else 1
+    if k + 1 != want:
+        raise JpegError(f"jpeg: {k + 1} restart intervals, {want} expected")
+    starts = np.concatenate([[0], mk[:k] + 2]) + pos
+    lens = mk[:k + 1] + pos - starts
+    return JpegStream(data, H, W, sampling, qtables, huff, restart, pos,
+                      tuple(zip(starts.tolist(), lens.tolist())))
+
+
+def decode_tables(huff) -> np.ndarray:
+    """int32 [4 * DEC_TABLE_WORDS], the decode tables of jpeg_entropy_dec.h for the four Huffman
+    specifications (DC luma, DC chroma, AC luma, AC chroma).  Per table, with ``code`` the canonical
+    code counter of T.81 Annex C: 256 uint16 look-ahead entries ``(length << 8) | symbol`` indexed
+    by the next 8 bits (0: the code is longer); ``limit[l-1]`` = the counter after the codes of
+    length l, left-justified to 16 bits; ``valoff[l-1]`` = index of the first value of length l
+    minus its code; the 256 value bytes."""
+    out = np.zeros((4, DEC_TABLE_WORDS), dtype=np.int32)
+    for t, (bits, vals) in enumerate(huff):
+        look = np.zeros(256, dtype=np.uint16)
+        code, k = 0, 0
+        for length in range(1, 17):
+            out[t, 128 + 16 + length - 1] = k - code
+            for _ in range(bits[length - 1]):
+                if length <= DEC_LOOK_BITS:
+                    lo = code << (DEC_LOOK_BITS - length)
+                    look[lo: lo + (1 << (DEC_LOOK_BITS - length))] = (length << 8) | vals[k]
+                code += 1
+                k += 1
+            out[t, 128 + length - 1] = code << (16 - length)
+            code <<= 1
+        out[t, :128] = look.view(np.int32)
+        hv = np.zeros(256, dtype=np.uint8)
+        hv[:len(vals)] = vals
+        out[t, 160:] = hv.view(np.int32)
+    return out.reshape(-1)
+
+
+class _BitReader:
+    """MSB-first bits of one unstuffed restart interval."""
+    __slots__ = ("buf", "pos", "acc", "n")
+
+    def __init__(self, raw: bytes) -> None:
+        stray = -1                       # a 0xFF not followed by 0x00 ends the data
+        i = raw.find(b"\xff")
+        while i >= 0:
+            if raw[i + 1: i + 2] != b"\x00":
+                stray = i
+                break
+            i = raw.find(b"\xff", i + 2)
+        if stray >= 0:
+            raw = raw[:stray]
+        self.buf = raw.replace(b"\xff\x00", b"\xff")
+        self.pos, self.acc, self.n = 0, 0, 0
+
+    def fill(self) -> None:
+        take = self.buf[self.pos: self.pos + 8]
+        self.pos += len(take)
+        self.acc = ((self.acc & ((1 << self.n) - 1)) << (8 * len(take))) | int.from_bytes(take, "big")
+        self.n += 8 * len(take)
+
+    def peek16(self) -> int:
+        if self.n < 16:
+            self.fill()
+        return (self.acc >> (self.n - 16)) & 0xFFFF if self.n >= 16 else (self.acc << (16 - self.n)) & 0xFFFF
+
+    def receive(self, s: int) -> int:
+        if self.n < s:
+            self.fill()
+            if self.n < s:
+                return -1
+        self.n -= s
+        return (self.acc >> self.n) & ((1 << s) - 1)
+
+
+def _decode_interval(raw: bytes, codebooks, qz, nb: int, nmcu: int, out: np.ndarray) -> int:
+    """One restart interval into ``out`` [nmcu, nb, 64] (zeroed); the status."""
+    rd = _BitReader(raw)
+    t2 = WIDE_T * WIDE_T
+
+    def symbol(book) -> int:
+        w = rd.peek16()
+        hit = book[0][w >> 8]
+        if hit:
+            length, sym = hit
+        else:
+            for length in range(9, 17):
+                sym = book[length].get(w >> (16 - length))
+                if sym is not None:
+                    break
+            else:
+                return -TRUNCATED if rd.n < 16 else -BAD_CODE
+        if length > rd.n:
+            return -TRUNCATED
+        rd.n -= length
+        return sym
+    pred = [0, 0, 0]
+    for m in range(nmcu):
+        for b in range(nb):
+            comp = 0 if b < nb - 2 else b - (nb - 2) + 1
+            tc = 1 if comp else 0
+            q = qz[tc]
+            s = symbol(codebooks[tc])
+            if s < 0:
+                return -s
+            if s > 11:
+                return BAD_CODE
+            if s:
+                v = rd.receive(s)
+                if v < 0:
+                    return TRUNCATED
+                pred[comp] += v if v >= (1 << (s - 1)) else v - (1 << s) + 1
+            d = pred[comp] * q[0]
+            if abs(d) > WIDE_T:
+                return WIDE
+            energy = d * d
+            out[m, b, 0] = pred[comp]
+            k = 1
+            while k < 64:
+                rs = symbol(codebooks[2 + tc])
+                if rs < 0:
+                    return -rs
+                r, s = rs >> 4, rs & 15
+                if s == 0:
+                    if rs == 0:
+                        break
+                    if r != 15:
+                        return BAD_CODE
+                    k += 16
+                    if k > 63:
+                        return OVERRUN
+                    continue
+                if s > 10:
+                    return BAD_CODE
+                k += r
+                if k > 63:
+                    return OVERRUN
+                v = rd.receive(s)
+                if v < 0:
+                    return TRUNCATED
+                v = v if v >= (1 << (s - 1)) else v - (1 << s) + 1
+                d = v * q[k]
+                if abs(d) > WIDE_T:
+                    return WIDE
+                energy += d * d
+                if energy > t2:
+                    return WIDE
+                out[m, b, k] = v
+                k += 1
+            if energy > t2:
+                return WIDE
+    return OK
+
+
+def _codebook(bits, vals):
+    """[look-ahead list of (length, symbol) by the next 8 bits] + {code: symbol} per length 9..16."""
+    book = [[None] * 256] + [dict() for _ in range(16)]
+    for sym, (code, length) in _huff_codes(bits, vals).items():
+        if length <= 8:
+            lo = code << (8 - length)
+            for i in range(lo, lo + (1 << (8 - length))):
+                book[0][i] = (length, sym)
+        else:
+            book[length][code] = sym
+    return book
+
+
+def entropy_decode(stream: JpegStream, first_interval: int = 0) -> np.ndarray:
+    """The quantised zig-zag coefficients int16 [mcus, blocks per MCU, 64] of a parsed stream: the
+    inverse of :func:`entropy`.  The first interval with a status other than OK raises
+    (``first_interval`` offsets the interval number reported, for a batch)."""
+    _, nb, mx, my = geometry(stream.H, stream.W, stream.sampling)
+    mcus = mx * my
+    per = stream.restart or mcus
+    books = [_codebook(b, v) for b, v in stream.huff]
+    qz = [[t[ZIGZAG[z]] for z in range(64)] for t in stream.qtables]
+    out = np.zeros((mcus, nb, 64), dtype=np.int16)
+    for it, (off, ln) in enumerate(stream.intervals):
+        m0 = it * per
+        st = _decode_interval(stream.data[off: off + ln], books, qz, nb, min(per, mcus - m0), out[m0: m0 + per])
+        if st != OK:
+            raise_status(st, first_interval + it)
+    return out
+
+
+def jpeg_decode(data) -> np.ndarray:
+    """Baseline JPEG bytes -> uint8 [H, W, 3], the pixels a libjpeg decoder (PIL) returns for them:
+    ``reconstruct(entropy_decode(parse(data)))`` with the stream's own quantisation tables."""
+    st = data if isinstance(data, JpegStream) else parse(data)
+    return reconstruct(entropy_decode(st), st.H, st.W, 0, st.sampling, tables=st.qtables)

@@ -20,7 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from .blur_format import box_params, gaussian_blur_pil  # noqa: F401  (PIL's GaussianBlur: the contract of ops/csrc/blur_pil.hip)
-from .jpeg_format import jpeg_decoded, jpeg_encode  # noqa: F401  (baseline JPEG: the contracts of ops/csrc/jpeg.hip)
+from .jpeg_format import jpeg_decode, jpeg_decoded, jpeg_encode  # noqa: F401  (baseline JPEG: the contracts of ops/csrc/jpeg.hip)
 
 
 def _act(y: torch.Tensor, act: Optional[str]) -> torch.Tensor:

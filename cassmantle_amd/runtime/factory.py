@@ -183,6 +183,32 @@ def build_content_jpeg_fn(cfg: Config, device: Optional[str] = None):
     return content_jpeg
 
 
+def build_jpeg_decode_fn(cfg: Config, device: Optional[str] = None):
+    """Stored JPEG bytes -> their decoded pixels in HBM (``gpu_jpeg_decode``): ``fn(jpeg) ->
+    DeviceImage``, one ops.jpeg_decode call on the calling thread's current stream, PIL's pixels
+    bit for bit.  ``fn`` returns ``None``, which leaves the stream to PIL on the host as without
+    the flag, for a stream with fewer than ``jpeg_decode_min_intervals`` restart intervals and for
+    bytes the decoder refuses (outside its scope, or malformed).  ``None`` unless
+    ``gpu_jpeg_decode`` and ``gpu_blur`` are set and the device is a GPU."""
+    dev = device or ("cuda" if torch.cuda.is_available() else "cpu")
+    m = cfg.model
+    if not (m.gpu_jpeg_decode and m.gpu_blur) or not str(dev).startswith("cuda"):
+        return None
+    from .. import ops
+    from ..game.content import DeviceImage
+    from ..ops import jpeg_format as jf
+
+    def jpeg_decode(jpeg: bytes):
+        try:
+            stream = jf.parse(jpeg)
+            if len(stream.intervals) < m.jpeg_decode_min_intervals:
+                return None
+            return DeviceImage(ops.jpeg_decode(stream, device=dev))
+        except (jf.JpegUnsupported, jf.JpegError):
+            return None
+    return jpeg_decode
+
+
 def build_prompt_generator(cfg: Config, device: Optional[str] = None):
     """synthetic (default, template grammar) | lm (local causal LM, models/lm.py) | remote
     (HF text-generation endpoint, reference parity).  ``None`` -> per-room synthetic."""
@@ -243,4 +269,6 @@ def build_service(cfg: Config, image_gen_for_room: Optional[Callable[[str], Imag
         kw["blur_jpeg_fn"] = build_blur_jpeg_fn(cfg)
     if "content_jpeg_fn" not in kw:
         kw["content_jpeg_fn"] = build_content_jpeg_fn(cfg)
+    if "decode_fn" not in kw:
+        kw["decode_fn"] = build_jpeg_decode_fn(cfg)
     return GameService(cfg, scorer, image_gen_for_room=image_gen_for_room, **kw)

@@ -34,6 +34,17 @@ the blur stage alone (HIP events around the 60 Gaussian launches + copies, and a
 batched launch) and whether the batched blur equals Pillow's GaussianBlur on this image.
 
     python tools/bench_jpeg.py --blur-kernel pil [--res 512 1024] [--reps 2] [--out profiles/blur_pil_prewarm.jsonl]
+
+``--decode`` measures what a blur cache does for a content version it holds only the stored bytes
+of: the parent's path (PIL ``decode_jpeg`` on the host, then the upload of the full-resolution
+pixels) against ``ops.jpeg_decode`` (``gpu_jpeg_decode``: the entropy-coded bytes are uploaded and
+decoded in HBM), each timed to a device synchronise, interleaved ``--reps`` times after a warm-up
+of each.  Streams: the GPU encoder's content JPEG at one MCU row, 16 and 4 MCUs per restart
+interval, and a PIL-encoded stream without restart markers (one lane decodes the whole image).
+Per record: host wall time, CPU time, bytes moved host to device, and per stream the device time
+(HIP events) of the zero + entropy decode launch and of the zero alone.
+
+    python tools/bench_jpeg.py --decode [--res 512 1024] [--reps 2] [--out profiles/jpeg_decode.jsonl]
 """
 import argparse
 import io
@@ -269,8 +280,84 @@ def content_main(a, emit) -> int:
     return 0
 
 
+def decode_main(a, emit) -> int:
+    """--decode: stored JPEG bytes -> blur source pixels in HBM (what BlurCache._source does for a
+    version with no device-resident source)."""
+    import numpy as np
+    import torch
+    from cassmantle_amd import ops
+    from cassmantle_amd.game.imaging import decode_jpeg, encode_jpeg
+    from cassmantle_amd.ops import jpeg_format as jf
+    from cassmantle_amd.ops._ext import ext
+    from cassmantle_amd.runtime.factory import _device_pixels
+
+    def entropy_device_ms(stream, iters: int = 5):
+        """(zero + entropy decode launch, zero alone) device time in ms, HIP events, nothing else queued"""
+        _, nb, mx, my = jf.geometry(stream.H, stream.W, stream.sampling)
+        staged, base, tables = ops._jpeg_decode_inputs([stream], torch.device("cuda"))
+        buf = torch.empty(mx * my * nb * 64 + 8, device="cuda", dtype=torch.int16)
+        best = [1e9, 1e9]
+        for _ in range(iters + 1):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            torch.cuda.synchronize()
+            ev[0].record()
+            ext().jpeg_entropy_decode(staged, base, tables, buf, 1, stream.H, stream.W,
+                                      int(stream.sampling == "420"), stream.restart)
+            ev[1].record()
+            ext().zero_(buf)
+            ev[2].record()
+            torch.cuda.synchronize()
+            best = [min(best[0], ev[0].elapsed_time(ev[1])), min(best[1], ev[1].elapsed_time(ev[2]))]
+        return best
+
+    for res in a.res:
+        img = source_image(res).copy()
+        t = torch.from_numpy(img).cuda()
+        mcu_row = (res + 15) // 16
+        streams = {f"in-tree, {r} MCUs per interval" + (" (one MCU row)" if r == mcu_row else ""):
+                   ops.jpeg_encode(t, QUALITY, "420", r)[0] for r in (mcu_row, 16, 4)}
+        streams["PIL, no DRI (one interval)"] = encode_jpeg(img, QUALITY)
+        for name, jpeg in streams.items():
+            st = jf.parse(jpeg)
+            staged_bytes = 8 * len(st.intervals) + st.intervals[-1][0] + st.intervals[-1][1] - st.scan_offset
+
+            def run_parent():
+                torch.cuda.synchronize()
+                w0, c0 = time.perf_counter(), time.process_time()
+                x = _device_pixels(decode_jpeg(jpeg), "cuda")
+                torch.cuda.synchronize()
+                wall, cpu = time.perf_counter() - w0, time.process_time() - c0
+                return x, {"res": res, "stream": name, "path": "parent (PIL decode + upload)",
+                           "intervals": len(st.intervals), "jpeg_bytes": len(jpeg), "wall_ms": round(wall * 1e3, 3),
+                           "cpu_ms": round(cpu * 1e3, 3), "h2d_bytes": res * res * 3}
+
+            def run_new():
+                torch.cuda.synchronize()
+                w0, c0 = time.perf_counter(), time.process_time()
+                x = ops.jpeg_decode(jpeg, device="cuda")
+                torch.cuda.synchronize()
+                wall, cpu = time.perf_counter() - w0, time.process_time() - c0
+                return x, {"res": res, "stream": name, "path": "ops.jpeg_decode", "intervals": len(st.intervals),
+                           "jpeg_bytes": len(jpeg), "wall_ms": round(wall * 1e3, 3), "cpu_ms": round(cpu * 1e3, 3),
+                           "h2d_bytes": (staged_bytes + 15) // 16 * 16}
+
+            xp, _ = run_parent()
+            xn, _ = run_new()
+            equal = bool(torch.equal(xp, xn))
+            for rep in range(a.reps):
+                emit(dict(run_parent()[1], rep=rep))
+                emit(dict(run_new()[1], rep=rep, equals_pil_decode=equal))
+            both, zero = entropy_device_ms(st)
+            emit({"res": res, "stream": name, "intervals": len(st.intervals),
+                  "zero_plus_entropy_decode_device_ms": round(both, 4), "zero_alone_device_ms": round(zero, 4),
+                  "kernels": "zero_kernel + jpeg_entropy_decode_kernel"})
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--decode", action="store_true",
+                    help="stored JPEG bytes -> device pixels: PIL decode + upload against ops.jpeg_decode")
     ap.add_argument("--res", type=int, nargs="+", default=[512, 1024])
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--out", default=None, help="also append the JSON records to this file")
@@ -299,8 +386,8 @@ def main(argv=None) -> int:
             sink.write(line + "\n")
             sink.flush()
 
-    if a.content or a.blur_kernel:
-        rc = content_main(a, emit) if a.content else blur_kernel_main(a, emit)
+    if a.decode or a.content or a.blur_kernel:
+        rc = decode_main(a, emit) if a.decode else (content_main(a, emit) if a.content else blur_kernel_main(a, emit))
         if sink:
             sink.close()
         return rc
