@@ -594,7 +594,8 @@ def lm_sample(logits: torch.Tensor, noise: torch.Tensor, eos_bias: torch.Tensor,
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, lens: torch.Tensor,
                      scale: Optional[float] = None) -> torch.Tensor:
     """One query token per sequence.  q [B, H, d]; caches [B, L, Hk, d]; lens [B] int32 (device)
-    valid keys per sequence.  Split-KV GQA kernel; graph-capturable (lens stays on device)."""
+    valid keys per sequence.  Split-KV GQA kernel; graph-capturable (lens stays on device).
+    A sequence with ``lens[b] == 0`` gets zeros (kernel and reference alike)."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     if not _use_hip(q):
         return ref.decode_attention(q, k_cache, v_cache, lens, scale)
@@ -644,7 +645,11 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional
               fp8: bool = False, kv8: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Flash attention.  q [B,Nq,H,d], k/v [B,Nk,H,d]; strided views allowed (last dim
     contiguous), e.g. slices of a fused QKV projection output.  Returns [B,Nq,H,d].
-    ``kv8``: K/V already packed by :func:`pack_kv_fp8` (fp8 path only)."""
+    ``kv8``: K/V already packed by :func:`pack_kv_fp8` (fp8 path only).
+
+    A query with no valid key (``kv_lens[b] == 0``) gets zeros: every HIP kernel and
+    ``ops.reference.attention`` agree on that.  The explicit ``torch`` baseline mode keeps
+    scaled_dot_product_attention's own result for such a row (NaN)."""
     d = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(d)
     if not _use_hip(q):

@@ -37,13 +37,20 @@ def _act(y: torch.Tensor, act: Optional[str]) -> torch.Tensor:
     raise ValueError(act)
 
 
-def linear(x, w, bias=None, residual=None, act=None, out_dtype=None):
+def _ct(dtype):
+    """``dtype=`` of the reference ops: the compute type (fp32 when None).  When given, the result
+    also comes back in it, unrounded (``torch.float64``: the oracle of tests/kernel_oracle.py)."""
+    return torch.float32 if dtype is None else dtype
+
+
+def linear(x, w, bias=None, residual=None, act=None, out_dtype=None, dtype=None):
     """y = act(x @ w^T + bias) + residual;  act='geglu': w is [2N, K] ->
     y = (x@w[:N]^T + b[:N]) * gelu(x@w[N:]^T + b[N:])."""
-    od = out_dtype or x.dtype
-    y = torch.matmul(x.float(), w.float().t())
+    od = out_dtype or dtype or x.dtype
+    ct = _ct(dtype)
+    y = torch.matmul(x.to(ct), w.to(ct).t())
     if bias is not None:
-        y = y + bias.float()
+        y = y + bias.to(ct)
     if act == "geglu":
         h, g = y.chunk(2, dim=-1)
         y = h * F.gelu(g)
@@ -53,58 +60,63 @@ def linear(x, w, bias=None, residual=None, act=None, out_dtype=None):
     else:
         y = _act(y, act)
     if residual is not None:
-        y = y + residual.float()
+        y = y + residual.to(ct)
     return y.to(od)
 
 
-def conv2d(x, w, bias=None, stride=1, padding=1, residual=None, upsample=False, chan_bias=None):
+def conv2d(x, w, bias=None, stride=1, padding=1, residual=None, upsample=False, chan_bias=None, dtype=None):
     """NHWC conv.  x [B,H,W,Cin], w [Cout,kh,kw,Cin].  ``upsample`` = nearest 2x on the input
     first (fused in the HIP kernel's address generation).  ``chan_bias`` [B, Cout] is a
     per-sample bias (ResNet time-embedding add fused into the epilogue)."""
-    xi = x.float().permute(0, 3, 1, 2)
+    ct = _ct(dtype)
+    xi = x.to(ct).permute(0, 3, 1, 2)
     if upsample:
         xi = F.interpolate(xi, scale_factor=2.0, mode="nearest")
-    wi = w.float().permute(0, 3, 1, 2)
-    y = F.conv2d(xi, wi, None if bias is None else bias.float(), stride=stride, padding=padding)
+    wi = w.to(ct).permute(0, 3, 1, 2)
+    y = F.conv2d(xi, wi, None if bias is None else bias.to(ct), stride=stride, padding=padding)
     y = y.permute(0, 2, 3, 1)
     if chan_bias is not None:
-        y = y + chan_bias.float()[:, None, None, :]
+        y = y + chan_bias.to(ct)[:, None, None, :]
     if residual is not None:
-        y = y + residual.float()
-    return y.to(x.dtype).contiguous()
+        y = y + residual.to(ct)
+    return y.to(dtype or x.dtype).contiguous()
 
 
-def group_norm(x, num_groups, weight, bias, eps, silu=False):
+def group_norm(x, num_groups, weight, bias, eps, silu=False, dtype=None):
     """NHWC GroupNorm (+ fused SiLU).  x [B, ..., C] (any spatial rank, channels last)."""
     B, C = x.shape[0], x.shape[-1]
-    xf = x.float().reshape(B, -1, num_groups, C // num_groups)
+    ct = _ct(dtype)
+    xf = x.to(ct).reshape(B, -1, num_groups, C // num_groups)
     mean = xf.mean(dim=(1, 3), keepdim=True)
     var = xf.var(dim=(1, 3), keepdim=True, unbiased=False)
     y = (xf - mean) * torch.rsqrt(var + eps)
-    y = y.reshape(B, -1, C) * weight.float() + bias.float()
+    y = y.reshape(B, -1, C) * weight.to(ct) + bias.to(ct)
     if silu:
         y = F.silu(y)
-    return y.reshape(x.shape).to(x.dtype)
+    return y.reshape(x.shape).to(dtype or x.dtype)
 
 
-def layer_norm(x, weight, bias, eps):
-    return F.layer_norm(x.float(), (x.shape[-1],), weight.float(), None if bias is None else bias.float(), eps).to(x.dtype)
+def layer_norm(x, weight, bias, eps, dtype=None):
+    ct = _ct(dtype)
+    return F.layer_norm(x.to(ct), (x.shape[-1],), weight.to(ct), None if bias is None else bias.to(ct),
+                        eps).to(dtype or x.dtype)
 
 
-def rms_norm(x, weight, eps):
-    xf = x.float()
-    return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * weight.float()).to(x.dtype)
+def rms_norm(x, weight, eps, dtype=None):
+    xf = x.to(_ct(dtype))
+    return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * weight.to(xf.dtype)).to(dtype or x.dtype)
 
 
-def rope(x, pos, theta):
+def rope(x, pos, theta, dtype=None):
     """Rotate-half rotary embedding.  x [B, T, h, d]; pos [B, T] int positions."""
     d = x.shape[-1]
-    inv = theta ** (-torch.arange(0, d // 2, device=x.device, dtype=torch.float32) * 2.0 / d)
-    ang = pos.float()[..., None] * inv                       # [B, T, d/2]
+    ct = _ct(dtype)
+    inv = theta ** (-torch.arange(0, d // 2, device=x.device, dtype=ct) * 2.0 / d)
+    ang = pos.to(ct)[..., None] * inv                        # [B, T, d/2]
     cos, sin = ang.cos()[:, :, None, :], ang.sin()[:, :, None, :]
-    xf = x.float()
+    xf = x.to(ct)
     x0, x1 = xf[..., : d // 2], xf[..., d // 2:]
-    return torch.cat([x0 * cos - x1 * sin, x1 * cos + x0 * sin], dim=-1).to(x.dtype)
+    return torch.cat([x0 * cos - x1 * sin, x1 * cos + x0 * sin], dim=-1).to(dtype or x.dtype)
 
 
 def rope_kv(qkv, pos0, q_out, k_cache, v_cache, H, Hk, theta):
@@ -122,28 +134,33 @@ def rope_kv(qkv, pos0, q_out, k_cache, v_cache, H, Hk, theta):
         v_cache[b, p0:p0 + n] = x[b, :n, H + Hk:]
 
 
-def decode_attention(q, k_cache, v_cache, lens, scale):
-    """q [B, H, d] one token vs cache [B, L, Hk, d] with lens[b] valid keys -> [B, H, d]."""
+def decode_attention(q, k_cache, v_cache, lens, scale, dtype=None):
+    """q [B, H, d] one token vs cache [B, L, Hk, d] with lens[b] valid keys -> [B, H, d].
+    A sequence with no valid key (``lens[b] == 0``) gets zeros, as from the HIP kernel."""
     B, H, d = q.shape
-    out = torch.empty_like(q)
+    out = torch.empty_like(q, dtype=dtype or q.dtype)
     for b in range(B):
         n = int(lens[b])
-        o = attention(q[b:b + 1, None], k_cache[b:b + 1, :n], v_cache[b:b + 1, :n], scale)
+        o = attention(q[b:b + 1, None], k_cache[b:b + 1, :n], v_cache[b:b + 1, :n], scale, dtype=dtype)
         out[b] = o[0, 0]
     return out
 
 
-def attention(q, k, v, scale=None, causal=False, kv_lens=None):
+def attention(q, k, v, scale=None, causal=False, kv_lens=None, dtype=None):
     """q [B,Nq,H,d], k/v [B,Nk,H,d] (any strides, last dim contiguous) -> o [B,Nq,H,d].
-    ``kv_lens`` [B] int: keys >= len are masked (padding mask)."""
+    ``kv_lens`` [B] int: keys >= len are masked (padding mask).  A query with no valid key
+    (``kv_lens[b] == 0``, or no keys at all) gets zeros, not the NaN of a softmax over nothing:
+    the contract of every HIP attention kernel (their ``inv = l > 0 ? 1 / l : 0``).  Keys past
+    ``kv_lens`` never reach the result: their K/V values may be anything, NaN and inf included."""
     d = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(d)
     if k.shape[2] != q.shape[2]:   # grouped-query attention: expand the kv heads
         g = q.shape[2] // k.shape[2]
         k, v = k.repeat_interleave(g, dim=2), v.repeat_interleave(g, dim=2)
-    qf = q.float().permute(0, 2, 1, 3)
-    kf = k.float().permute(0, 2, 1, 3)
-    vf = v.float().permute(0, 2, 1, 3)
+    ct = _ct(dtype)
+    qf = q.to(ct).permute(0, 2, 1, 3)
+    kf = k.to(ct).permute(0, 2, 1, 3)
+    vf = v.to(ct).permute(0, 2, 1, 3)
     s = torch.matmul(qf, kf.transpose(-1, -2)) * scale
     Nq, Nk = s.shape[-2], s.shape[-1]
     if causal:
@@ -153,9 +170,13 @@ def attention(q, k, v, scale=None, causal=False, kv_lens=None):
         ar = torch.arange(Nk, device=s.device)
         m = ar[None, :] >= kv_lens.to(s.device)[:, None]
         s = s.masked_fill(m[:, None, None, :], float("-inf"))
-    p = torch.softmax(s, dim=-1)
-    o = torch.matmul(p, vf).permute(0, 2, 1, 3)
-    return o.to(q.dtype).contiguous()
+    empty = torch.isneginf(s).all(dim=-1, keepdim=True)      # queries with no valid key
+    p = torch.softmax(s.masked_fill(empty, 0.0), dim=-1)
+    if kv_lens is not None:
+        # a masked key contributes nothing whatever its V holds (p = 0 times inf would be NaN)
+        vf = vf.masked_fill(m[:, None, :, None], 0.0)
+    o = torch.matmul(p, vf).masked_fill(empty, 0.0).permute(0, 2, 1, 3)
+    return o.to(dtype or q.dtype).contiguous()
 
 
 def gather_cosine(table, ia, ib):

@@ -1,0 +1,260 @@
+"""The instruments of kernel_oracle.py, proven on the CPU with ``ops.reference`` as the kernel:
+the ideal kernel (fp64 math, one rounding where the HIP kernels round) stays under half the bound
+in every block of every case test_kernel_edges_gpu.py runs, and each planted bug -- all of which
+the whole-tensor error of tests/test_kernels_gpu.py lets through -- fails its check."""
+import math
+
+import pytest
+import torch
+
+import kernel_oracle as ko
+from cassmantle_amd import ops
+from cassmantle_amd.ops import reference as ref
+from kernel_oracle import BF16, BOUND, F64, bf16_round, block_rel_err
+from test_gemm_menu import header_rows
+
+FLOOR = {}      # family -> the ideal kernel's worst block over the cases run so far
+
+
+def floor(family, err, what):
+    FLOOR[family] = max(FLOOR.get(family, 0.0), err)
+    assert err < 0.5 * BOUND[family], (family, what, err)
+
+
+def global_rel_err(out, ref64):
+    return ((out.to(F64) - ref64).norm() / ref64.norm()).item()
+
+
+# ------------------------------------------------------------------------------ the ideal kernel passes
+def test_ideal_gemm():
+    for c in ko.gemm_cases(header_rows()):
+        x, w, b, r = ko.gemm_inputs(c)
+        y64 = ko.linear64(x, w, b, r, c.act)
+        floor("gemm", block_rel_err(bf16_round(y64), y64), c.id)
+    for M, N, K in ko.AREG_CASES:
+        x, w, b, r = ko.gemm_inputs(ko.GemmCase(15, 1, M, N, K, "silu"))
+        y64 = ko.linear64(x, w, b, r, "silu")
+        floor("gemm", block_rel_err(bf16_round(y64), y64), ("areg", M, N, K))
+        for n in (N, ko.AREG_FALLBACK_N):
+            x, g, be, w, b = ko.ln_fold_inputs(M, n, K, seed=M + K)
+            floor("ln_fold", block_rel_err(ko.ideal_ln_fold(x, g, be, w, b), ko.ln_linear64(x, g, be, w, b)), (M, n, K))
+    for _, N, K in ko.AREG_CASES[:2] + [(0, ko.AREG_FALLBACK_N, 320), (0, ko.AREG_FALLBACK_N, 640)]:   # gn_linear: B = 1, S = 256
+        x, g, be, w, b = ko.ln_fold_inputs(256, N, K, seed=K)
+        x = x[None]
+        y64 = ko.gn_linear64(x, g, be, 32, 1e-6, w, b)
+        xn = ref.group_norm(x, 32, g, be, 1e-6, False, dtype=F64).to(BF16)      # the A rows the MFMA sees
+        floor("gn_fold", block_rel_err(bf16_round(ko.linear64(xn, w, b))[0], y64[0]), ("gn", K))
+    for Ca, Cb in ko.CAT_CASES:
+        x, w, b, _ = ko.gemm_inputs(ko.GemmCase(-1, 0, 129, ko.CAT_N, Ca + Cb, "none"))
+        y64 = ko.linear64(x, w, b)
+        floor("gemm", block_rel_err(bf16_round(y64), y64), ("cat", Ca, Cb))
+    M, N, K = ko.ROW_STATS_CASE
+    x, g, be, w, b = ko.ln_fold_inputs(M, 72, N, seed=77)
+    floor("ln_fold", block_rel_err(ko.ideal_ln_fold(x, g, be, w, b), ko.ln_linear64(x, g, be, w, b)), "row_stats")
+
+
+def test_ideal_conv():
+    for B, H, W, Cin, Cout, stride in ko.CONV_CASES:
+        args = ko.conv_inputs(B, H, W, Cin, Cout, stride)
+        y64 = ko.conv64(*args, stride=stride).flatten(0, 2)
+        floor("conv", block_rel_err(bf16_round(y64), y64), (B, H, W, Cin, Cout, stride))
+    B, H, W, Cin, Cout = ko.UP2_CASE
+    for cin in (Cin, ko.UP2_SPLIT_CIN):
+        y64 = ko.conv64(*ko.conv_inputs(B, H, W, cin, Cout, up=True), up=True).flatten(0, 2)
+        floor("conv", block_rel_err(bf16_round(y64), y64), ("up2", cin))
+
+
+@pytest.mark.parametrize("d", [32, 40, 64, 80, 160, 256, 512])
+def test_ideal_attention(d):
+    cases = ko.attn_cases(d) + ([ko.GQA_CASE] if d == 64 else []) + ([ko.D512_SPLIT_CASE] if d == 512 else [])
+    for c in cases:
+        q, k, v = ko.attn_data(c)
+        o64 = ko.attention64(q, k, v, c.lens, c.causal)
+        floor("attention", block_rel_err(ko.ideal_attention(q, k, v, c.lens, c.causal), o64, (1, 16, 1, None)), c.id)
+        if d == 64:
+            floor("fp8", block_rel_err(ko.ideal_attention(q, k, v, c.lens, c.causal, fp8=True), o64, (1, 16, 1, None)), c.id)
+
+
+def test_ideal_decode_attention():
+    for L in ko.DECODE_L:
+        for g in ko.DECODE_GROUPS:
+            q, kc, vc, lens = ko.decode_data(L, g)
+            o64 = ko.decode64(q, kc, vc, lens)
+            o = ko.ideal_attention(q[:, None], kc, vc, lens)[:, 0]
+            floor("decode", block_rel_err(o, o64, (1, 1, None)), (L, g))
+            # ops.reference.decode_attention is the same function up to its fp32 math
+            assert block_rel_err(ref.decode_attention(q, kc, vc, torch.tensor(lens), 64 ** -0.5), o64, (1, 1, None)) < BOUND["decode"]
+
+
+def test_ideal_norms_and_rope():
+    for rows, D in ko.ROW_NORM_CASES:
+        x, g, b = ko.norm_inputs(rows, D)
+        for y64 in (ref.layer_norm(x, g, b, 1e-5, dtype=F64), ref.rms_norm(x, g, 1e-5, dtype=F64)):
+            floor("norm", block_rel_err(bf16_round(y64), y64, (1, None)), (rows, D))
+        word, ids, pos, add = ko.embed_inputs(rows, D)
+        y64 = ko.embed_ln64(word, ids, pos, add, g, b)
+        floor("norm", block_rel_err(bf16_round(y64), y64, (1, 1, None)), ("embed", rows, D))
+    for B, S, C, G in ko.GN_CASES:
+        x, g, b = ko.gn_inputs(B, S, C)
+        for silu in (False, True):
+            y64 = ref.group_norm(x, G, g, b, 1e-5, silu, dtype=F64)
+            floor("group_norm", block_rel_err(bf16_round(y64), y64, (1, 16, C // G)), (B, S, C, G, silu))
+    for B, T, H, Hk, d, L, pos0 in ko.ROPE_CASES:
+        qkv = ko.rnd(B, T, (H + 2 * Hk) * d, seed=T + d)
+        for y64 in ko.rope64(qkv, pos0, H, Hk, d):
+            floor("rope", block_rel_err(bf16_round(y64), y64, (1, 1, 1, None)), (B, T, H, Hk, d))
+
+
+def test_floor_table():
+    """prints the table of kernel_oracle.py's docstring (run the whole file with -s)"""
+    if not FLOOR:
+        pytest.skip("run together with the ideal-kernel tests")
+    for fam in sorted(FLOOR):
+        print(f"{fam:12s} bound {BOUND[fam]:.3g}  ideal kernel's worst block {FLOOR[fam]:.2e}")
+        assert FLOOR[fam] < 0.5 * BOUND[fam]
+
+
+# ------------------------------------------------------------------------------ planted bugs
+def _linear_257():
+    """the smallest shape of test_kernels_gpu.py::test_gemm, with its bias and residual"""
+    x, w, b, r = ko.rnd(257, 320, seed=1), ko.rnd(320, 320, scale=320 ** -0.5, seed=2), ko.rnd(320, scale=0.1, seed=3), ko.rnd(257, 320, seed=4)
+    return x, w, b, r, ko.linear64(x, w, b, r)
+
+
+def test_bias_dropped_in_the_last_row_fails():
+    x, w, b, r, y64 = _linear_257()
+    bad = y64.clone()
+    bad[-1] = ko.linear64(x[-1:], w, None, r[-1:])[0]
+    bad = bf16_round(bad)
+    assert global_rel_err(bad, y64) < 1e-2                    # the whole-tensor check lets it through
+    assert block_rel_err(bad, y64) > 2 * BOUND["gemm"]
+    assert block_rel_err(bf16_round(y64), y64) < 0.5 * BOUND["gemm"]
+
+
+def test_bias_dropped_in_the_last_8_columns_fails():
+    x, w, b, r, y64 = _linear_257()
+    bad = y64.clone()
+    bad[:, -8:] = ko.linear64(x, w[-8:], None, r[:, -8:])
+    bad = bf16_round(bad)
+    assert global_rel_err(bad, y64) < 1e-2
+    assert block_rel_err(bad, y64) > 2 * BOUND["gemm"]
+
+
+def test_row_group_with_another_rows_layernorm_statistics_fails():
+    M, N, K = 129, 72, 320
+    x, g, be, w, b = ko.ln_fold_inputs(M, N, K, seed=9)
+    y64 = ko.ln_linear64(x, g, be, w, b)
+    wf, _, bf = ops.ln_fold(g, be, w, b)
+    xd = x.to(F64)
+    mean, rstd = xd.mean(-1, keepdim=True), (xd.var(-1, unbiased=False, keepdim=True) + 1e-5).rsqrt()
+    mean[16:32], rstd[16:32] = mean[0], rstd[0]               # one 16-row group: row 0's statistics
+    bad = bf16_round(rstd * (xd @ wf.to(F64).t() - mean * wf.to(F64).sum(1)) + bf.to(F64))
+    assert block_rel_err(bad, y64) > BOUND["ln_fold"]
+    assert block_rel_err(ko.ideal_ln_fold(x, g, be, w, b), y64) < 0.5 * BOUND["ln_fold"]
+
+
+@pytest.mark.parametrize("Nk", [63, 64, 65, 129])
+def test_key_past_kv_lens_included_fails(Nk):
+    c = ko.AttnCase(3, 33, Nk, 2, 2, 64, (Nk, 1, 0), False)
+    q, k, v = ko.attn_data(c)
+    o64 = ko.attention64(q, k, v, c.lens)
+    assert block_rel_err(ko.ideal_attention(q, k, v, c.lens, extra_key=True), o64, (1, 16, 1, None)) > BOUND["attention"]
+    assert block_rel_err(ko.ideal_attention(q, k, v, c.lens), o64, (1, 16, 1, None)) < 0.5 * BOUND["attention"]
+
+
+@pytest.mark.parametrize("causal", [False, True])
+def test_last_valid_key_dropped_fails(causal):
+    c = ko.AttnCase(3, 65, 65, 2, 2, 64, None if causal else (65, 1, 0), causal)
+    q, k, v = ko.attn_data(c)
+    o64 = ko.attention64(q, k, v, c.lens, causal)
+    assert block_rel_err(ko.ideal_attention(q, k, v, c.lens, causal, drop_last=True), o64, (1, 16, 1, None)) > BOUND["attention"]
+
+
+def test_causal_future_key_included_fails():
+    c = ko.attn_cases(64)[-1]
+    q, k, v = ko.attn_data(c)
+    o64 = ko.attention64(q, k, v, None, True)
+    assert block_rel_err(ko.ideal_attention(q, k, v, None, True, extra_key=True), o64, (1, 16, 1, None)) > BOUND["attention"]
+
+
+def test_decode_key_past_lens_or_dropped_fails():
+    q, kc, vc, lens = ko.decode_data(129, 2)
+    o64 = ko.decode64(q, kc, vc, lens)
+    for bug in ({"extra_key": True}, {"drop_last": True}):
+        assert block_rel_err(ko.ideal_attention(q[:, None], kc, vc, lens, **bug)[:, 0], o64, (1, 1, None)) > BOUND["decode"]
+
+
+def test_element_written_past_the_output_fails():
+    for shape, dtype in (((257, 72), BF16), ((3, 33, 2, 64), BF16), ((2, 8, 2), torch.int64), ((5,), torch.float32)):
+        g = ko.guarded(shape, dtype)
+        assert g.view.is_contiguous() and tuple(g.view.shape) == shape
+        assert g.guard * g.view.element_size() >= min(256 * shape[-1] * g.view.element_size(), 1 << 20)
+        g.view.zero_()
+        ko.check_guards(g)
+        for off in (g.guard + g.view.numel(), g.guard - 1, 0, g.buf.numel() - 1):
+            h = ko.guarded(shape, dtype)
+            h.view.zero_()
+            ko.int_view(h.buf)[off] = 0
+            assert not ko.guards_intact(h)
+            with pytest.raises(AssertionError):
+                ko.check_guards(h)
+    # an unwritten output element is a NaN of the pattern: the block error sees it
+    g = ko.guarded((17, 24))
+    y64 = torch.ones(17, 24, dtype=F64)
+    g.view.fill_(1.0)
+    assert block_rel_err(g.view, y64) == 0.0
+    ko.int_view(g.view)[16, 23] = g.pattern
+    assert block_rel_err(g.view, y64) == math.inf
+
+
+def test_nan_read_past_the_k_columns_of_a_strided_x_fails():
+    x, w, b, r, y64 = _linear_257()
+    xs = ko.poisoned(x, strided=True)
+    assert torch.equal(xs, x) and xs.stride(0) > x.shape[1] and not xs.is_contiguous()
+    assert block_rel_err(bf16_round(ko.linear64(xs, w, b, r)), y64) < 0.5 * BOUND["gemm"]
+    # a kernel that loads one more 8-wide chunk of every row and multiplies it by zero weights
+    wide = torch.as_strided(xs, (257, 328), xs.stride(), xs.storage_offset())
+    wz = torch.cat([w, torch.zeros(320, 8, dtype=BF16)], dim=1)
+    assert block_rel_err(bf16_round(ko.linear64(wide, wz, b, r)), y64) == math.inf
+    # contiguous operands: the rows before and after are NaN
+    xc = ko.poisoned(x)
+    assert xc.is_contiguous() and torch.equal(xc, x)
+    flat = torch.as_strided(xc, (x.numel() + 2,), (1,), xc.storage_offset() - 1)
+    assert math.isnan(flat[0].item()) and math.isnan(flat[-1].item())
+    q = ko.poisoned(ko.rnd(3, 5, 2, 16), strided=True, row_dims=2)
+    assert q.stride(1) == 2 * 16 + 16 and q.stride(2) == 16 and all(s % 8 == 0 for s in q.stride()[:3])
+
+
+def test_block_rel_err_blocks():
+    r = torch.ones(33, 20, dtype=F64)
+    o = r.clone()
+    o[32, 19] = 2.0                                            # the 1 x 4 corner block
+    assert block_rel_err(o, r) == pytest.approx(0.5)
+    assert block_rel_err(o, r, (None, None)) == pytest.approx(1 / math.sqrt(660))
+    z = torch.zeros(4, 8, dtype=F64)
+    assert block_rel_err(z, z, (1, None)) == 0.0
+    o = z.clone()
+    o[3, 0] = 1e-3                                             # a zero reference row must be zero exactly
+    assert block_rel_err(o, z, (1, None)) == math.inf
+
+
+# ------------------------------------------------------------------------------ the empty-row contract
+def test_attention_without_a_valid_key_is_zero():
+    q, k, v = ko.rnd(3, 5, 2, 16, seed=1), ko.rnd(3, 7, 2, 16, seed=2), ko.rnd(3, 7, 2, 16, seed=3)
+    lens = torch.tensor([7, 1, 0], dtype=torch.int32)
+    o = ref.attention(q, k, v, kv_lens=lens)
+    assert o.dtype == BF16 and torch.isfinite(o.float()).all()
+    assert not o[2].any() and o[0].any() and o[1].any()
+    assert torch.equal(o[:2], ref.attention(q[:2], k[:2], v[:2], kv_lens=lens[:2]))
+    assert torch.equal(o[0], ref.attention(q[:1], k[:1], v[:1])[0])                # full rows: as before
+    assert torch.equal(o[1], ref.attention(q[1:2], k[1:2, :1], v[1:2, :1])[0])
+    assert torch.equal(ops.attention(q, k, v, kv_lens=lens), o)                    # CPU dispatch
+    # masked K/V never reach the result, whatever they hold
+    k2, v2 = k.clone(), v.clone()
+    k2[1, 1:], v2[1, 1:], v2[2] = math.nan, math.inf, math.nan
+    assert torch.equal(ref.attention(q, k2, v2, kv_lens=lens), o)
+    kc, vc = ko.rnd(3, 9, 2, 16, seed=4), ko.rnd(3, 9, 2, 16, seed=5)
+    qd = ko.rnd(3, 4, 16, seed=6)
+    od = ref.decode_attention(qd, kc, vc, torch.tensor([9, 0, 4]), 0.25)
+    assert torch.isfinite(od.float()).all() and not od[1].any() and od[0].any() and od[2].any()
+    assert torch.equal(ops.decode_attention(qd, kc, vc, torch.tensor([9, 0, 4]), 0.25), od)
