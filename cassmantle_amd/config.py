@@ -145,6 +145,15 @@ class ModelConfig:
     # upload in both repetitions at 512^2 and 1024^2 (profiles/jpeg_decode.jsonl; at 32 it ties,
     # and a stream without restart markers, one lane for the whole image, is 13x slower)
     jpeg_decode_min_intervals: int = 64
+    # a stream with fewer intervals than that (PIL's content JPEGs have no restart markers: one
+    # interval) is decoded on the GPU as well, one lane per jpeg_decode_chunk_bytes of an interval
+    # (ops.jpeg_decode(mode="chunked"): self-synchronising chunks) instead of being left to PIL.
+    # Needs gpu_jpeg_decode, without which it does nothing.  Off: today's path
+    jpeg_decode_chunked: bool = False
+    # 16: the fastest of 16 / 32 / 64 / 128 on the bench image at 512^2 in both repetitions, and
+    # equal to 32 at 1024^2, where more than 1024 chunks raise it to 32 anyway
+    # (profiles/jpeg_decode_chunked.jsonl)
+    jpeg_decode_chunk_bytes: int = 16
     # the GPU blur itself: gaussian (a true fp32 Gaussian, ops.gaussian_blur) | pil (Pillow's
     # GaussianBlur = three integer box passes per axis, bit for bit: ops.gaussian_blur_pil).  With
     # pil the masked pixels are those blur_pil gives on a CPU front-end and those of the reference

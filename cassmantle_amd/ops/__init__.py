@@ -923,10 +923,12 @@ def _jpeg_decode_plan(device, stream):
     return plan
 
 
-def _jpeg_decode_inputs(streams, device):
+def _jpeg_decode_inputs(streams, device, extra=None):
     """The device inputs of one decode of parsed ``streams`` (one header key): the staged uint8
     buffer (interval table, then every stream's entropy-coded segment, scan start .. EOI) after its
-    one non-blocking copy from pinned memory, the number of bytes behind the table, the tables."""
+    one non-blocking copy from pinned memory, the number of bytes behind the table, the tables.
+    ``extra``: uint32 words staged behind the (padded) bytes in the same copy; their byte offset is
+    returned as a fourth value."""
     import numpy as np
     s0 = streams[0]
     B, nint = len(streams), len(s0.intervals)
@@ -942,18 +944,49 @@ def _jpeg_decode_inputs(streams, device):
     if base >= 2 ** 32 - 1:
         raise ValueError("jpeg_decode: batch too large for 32-bit byte offsets")
     nstage = (8 * B * nint + base + 15) // 16 * 16           # padded: word reads stay inside
-    stage = torch.empty(nstage, dtype=torch.uint8, pin_memory=True)
+    nextra = 0 if extra is None else 4 * extra.size
+    stage = torch.empty(nstage + nextra, dtype=torch.uint8, pin_memory=True)
     host = stage.numpy()
+    if extra is not None:
+        host[nstage:] = np.ascontiguousarray(extra, dtype=np.uint32).reshape(-1).view(np.uint8)
+        host = host[:nstage]
     host[: 8 * B * nint] = ivals.reshape(-1).view(np.uint8)
     p = 8 * B * nint
     for seg in segs:
         host[p: p + len(seg)] = np.frombuffer(seg, dtype=np.uint8)
         p += len(seg)
     host[p:] = 0
+    if extra is not None:
+        return stage.to(device, non_blocking=True), base, _jpeg_decode_plan(device, s0), nstage
     return stage.to(device, non_blocking=True), base, _jpeg_decode_plan(device, s0)
 
 
-def jpeg_decode(data, device=None, out=None):
+def _jpeg_chunk_groups(lens, cb: int):
+    """The work division of the chunked entropy decode for interval lengths ``lens`` [B, nint] and
+    chunk size ``cb``: (lane0 uint32 [B * nint], groups uint32 [G, 2], lanes per workgroup, chunks).
+    A group is a run of consecutive intervals of one image with at most 1024 chunks in all;
+    lane0 is the interval's first lane within its group."""
+    import numpy as np
+    from . import jpeg_format as jf
+    B, nint = lens.shape
+    nch = (lens + cb - 1) // cb
+    cum = np.cumsum(nch, axis=1)
+    lane0 = np.zeros((B, nint), dtype=np.int64)
+    groups, widest = [], 1
+    for b in range(B):
+        i, done = 0, 0                   # done = chunks of this image before interval i
+        while i < nint:
+            j = int(np.searchsorted(cum[b], done + jf.SYNC_MAX_CHUNKS, side="right"))     # intervals i .. j-1 fit
+            j = min(max(j, i + 1), min(nint, i + jf.SYNC_MAX_CHUNKS))
+            lane0[b, i:j] = cum[b, i:j] - nch[b, i:j] - done
+            groups.append((b * nint + i, j - i))
+            widest = max(widest, int(cum[b, j - 1]) - done)
+            done, i = int(cum[b, j - 1]), j
+    threads = min(jf.SYNC_MAX_CHUNKS, (widest + 63) // 64 * 64)
+    return lane0.reshape(-1).astype(np.uint32), np.asarray(groups, dtype=np.uint32), threads, int(nch.sum())
+
+
+def jpeg_decode(data, device=None, out=None, mode="interval", chunk_bytes=32, info=None):
     """Baseline JPEG bytes -> uint8 ``[H, W, 3]`` on ``device``: the pixels a libjpeg decoder (PIL)
     returns for them, bit for bit ``ops.reference.jpeg_decode`` (the entropy decode and decode
     contracts: ops/csrc/jpeg.hip).  ``data``: ``bytes`` (or a parsed ``jpeg_format.JpegStream``), or
@@ -967,9 +1000,21 @@ def jpeg_decode(data, device=None, out=None):
     pinned staging buffer and one host-to-device copy of the interval table and the entropy-coded
     bytes (the tables are uploaded once per identical header), zero + entropy decode (one lane per
     restart interval), inverse DCT + colour, and one 8-byte device-to-host copy of the status
-    word: the only synchronisation."""
+    word: the only synchronisation.
+
+    ``mode="chunked"`` decodes the same bytes with one lane per ``chunk_bytes`` (>= 16) bytes of
+    an interval instead of one per interval (the chunked entropy decode contract: jpeg.hip), for
+    streams with few or no restart markers: sync rounds + write pass, DC prefix sums and the block
+    check replace the entropy decode kernel, and the status copy (32 bytes) carries the flag, the
+    rounds and the completed blocks as well.  A flagged call runs the interval kernel on the same
+    staged bytes, which decides what is raised.  The result and the exceptions are those of
+    ``mode="interval"``; on a CPU tensor it is ``jpeg_format.entropy_decode_chunked``.  ``info``,
+    a dict, receives ``chunks``, ``rounds``, ``chunk_bytes`` (the effective value) and
+    ``serial_fallback``.  Any other ``mode`` is a ``ValueError``."""
     from . import jpeg_format as jf
     import numpy as np
+    if mode not in ("interval", "chunked"):
+        raise ValueError(f"jpeg_decode: mode must be 'interval' or 'chunked', not {mode!r}")
     single = isinstance(data, (bytes, bytearray, memoryview, jf.JpegStream))
     items = [data] if single else list(data)
     if not items:
@@ -987,12 +1032,35 @@ def jpeg_decode(data, device=None, out=None):
             raise ValueError(f"jpeg_decode: out must be a contiguous uint8 {list(want)} buffer on the device")
         dev = out.device
     probe = out if out is not None else torch.empty(0, device=dev)
+    chunked = mode == "chunked"
+    if chunked:
+        longest = max(ln for s in streams for _, ln in s.intervals)
+        cb = jf.chunk_bytes_for(longest, chunk_bytes)
+        if longest >= jf.SYNC_MAX_LEN:
+            raise jf.JpegUnsupported("jpeg: a restart interval of 2^28 bytes or more")
+    if chunked and not _use_hip(probe):
+        coefs, found = [], dict(chunks=0, rounds=0, chunk_bytes=cb, serial_fallback=False)
+        for i, s in enumerate(streams):
+            st = {}
+            try:
+                coefs.append(jf.entropy_decode_chunked(s, cb, i * len(s.intervals), st))
+            finally:
+                if st:
+                    found.update(chunks=found["chunks"] + st["chunks"], rounds=max(found["rounds"], st["rounds"]),
+                                 serial_fallback=found["serial_fallback"] or st["serial_fallback"])
+                if info is not None:
+                    info.update(found)
+        px = np.stack([jf.reconstruct(c, H, W, 0, s.sampling, tables=s.qtables) for c, s in zip(coefs, streams)])
+        res = torch.from_numpy(px[0] if single else px).to(dev)
+        return res if out is None else out.copy_(res)
     if not _use_hip(probe):
         px = np.stack([jf.reconstruct(jf.entropy_decode(s, i * len(s.intervals)), H, W, 0, s.sampling,
                                       tables=s.qtables) for i, s in enumerate(streams)])
         res = torch.from_numpy(px[0] if single else px).to(dev)
         return res if out is None else out.copy_(res)
     _, nb, mx, my = jf.geometry(H, W, s0.sampling)
+    if chunked:
+        return _jpeg_decode_chunked(streams, probe.device, out, single, cb, info)
     staged, base, tables = _jpeg_decode_inputs(streams, probe.device)
     ncoef = B * mx * my * nb * 64
     buf = torch.empty(ncoef + 8, device=probe.device, dtype=torch.int16)
@@ -1006,6 +1074,40 @@ def jpeg_decode(data, device=None, out=None):
     status = int(buf[ncoef: ncoef + 4].view(torch.int64).cpu().item()) & (2 ** 64 - 1)      # the only sync
     if status:
         jf.raise_status(status & 0xFFFFFFFF, 0xFFFFFFFF - (status >> 32))
+    return res
+
+
+def _jpeg_decode_chunked(streams, device, out, single, cb, info):
+    """The HIP path of ``jpeg_decode(mode="chunked")`` on the current stream."""
+    from . import jpeg_format as jf
+    import numpy as np
+    s0 = streams[0]
+    B, H, W = len(streams), s0.H, s0.W
+    _, nb, mx, my = jf.geometry(H, W, s0.sampling)
+    lens = np.asarray([[ln for _, ln in s.intervals] for s in streams], dtype=np.int64)
+    lane0, groups, threads, chunks = _jpeg_chunk_groups(lens, cb)
+    staged, base, tables, extra = _jpeg_decode_inputs(streams, device, np.concatenate([lane0, groups.reshape(-1)]))
+    ncoef = B * mx * my * nb * 64
+    buf = torch.empty(ncoef + 16, device=device, dtype=torch.int16)
+    s420 = int(s0.sampling == "420")
+    ext().jpeg_entropy_decode_chunked(staged, base, tables, buf, B, H, W, s420, s0.restart, extra, len(groups), cb,
+                                      threads)
+    planes = torch.empty(ncoef, device=device, dtype=torch.uint8)
+    res = out if out is not None else torch.empty((H, W, 3) if single else (B, H, W, 3), device=device,
+                                                  dtype=torch.uint8)
+    coef = buf[:ncoef].view(B, mx * my, nb, 64)
+    ext().jpeg_reconstruct(coef, tables[:672], planes, res.view(B, H, W, 3), H, W, s420)
+    # the only sync of a stream that decodes: status (0 here), flag, rounds, blocks completed
+    words = buf[ncoef: ncoef + 16].view(torch.int32).cpu().tolist()
+    fallback = bool(words[2]) or (words[4] & 0xFFFFFFFF) != B * mx * my * nb
+    if info is not None:
+        info.update(chunks=chunks, rounds=words[3], chunk_bytes=cb, serial_fallback=fallback)
+    if fallback:                         # the interval kernel decides what the stream's fault is called
+        ext().jpeg_entropy_decode(staged, base, tables, buf[: ncoef + 8], B, H, W, s420, s0.restart)
+        ext().jpeg_reconstruct(coef, tables[:672], planes, res.view(B, H, W, 3), H, W, s420)
+        status = int(buf[ncoef: ncoef + 4].view(torch.int64).cpu().item()) & (2 ** 64 - 1)
+        if status:
+            jf.raise_status(status & 0xFFFFFFFF, 0xFFFFFFFF - (status >> 32))
     return res
 
 

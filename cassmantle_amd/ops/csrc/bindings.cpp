@@ -983,6 +983,55 @@ void jpeg_entropy_decode(const at::Tensor& staged, int64_t nbytes, const at::Ten
   launch_jpeg_entropy_decode(a, d, cur_stream());
 }
 
+// The chunked entropy decode of the same inputs (chunked entropy decode contract: jpeg.hip).  staged
+// additionally holds, from byte `extra` on (a multiple of 4 at or behind the bytes), uint32
+// lane0 [B * intervals] and groups [ngroups][2]; buf int16 [B * mcus * blocks * 64 + 16]: the
+// coefficients, the status word (left 0 here), then uint32 flag, rounds, blocks completed, 0.
+// chunk = the effective chunk bytes, threads = lanes per workgroup.
+void jpeg_entropy_decode_chunked(const at::Tensor& staged, int64_t nbytes, const at::Tensor& tables, at::Tensor& buf,
+                                 int64_t B, int64_t H, int64_t W, int64_t s420, int64_t restart, int64_t extra,
+                                 int64_t ngroups, int64_t chunk, int64_t threads) {
+  CHECK_DEV(staged); CHECK_CONTIG(staged); CHECK_DEV(tables); CHECK_CONTIG(tables); CHECK_DEV(buf); CHECK_CONTIG(buf);
+  TORCH_CHECK(B > 0 && H > 0 && W > 0 && H < 65536 && W < 65536, "jpeg: image sides must be in 1..65535");
+  TORCH_CHECK(restart >= 0 && restart < 65536, "jpeg: restart interval 0..65535");
+  TORCH_CHECK(tables.scalar_type() == at::kInt && tables.numel() == 128 + 544 + 1024,
+              "jpeg: decode tables int32 [672 + 1024]");
+  JpegArgs a;
+  a.B = (int)B; a.H = (int)H; a.W = (int)W;
+  const int mcu = s420 ? 16 : 8;
+  a.nb = s420 ? 6 : 3;
+  a.mx = (a.W + mcu - 1) / mcu; a.my = (a.H + mcu - 1) / mcu;
+  const long long mcus = (long long)a.mx * a.my;
+  a.restart = restart ? (int)restart : (int)mcus;
+  a.nint = (int)((mcus + a.restart - 1) / a.restart);
+  const long long nivals = B * a.nint, ncoef = B * mcus * a.nb * 64;
+  TORCH_CHECK(nivals < 2147483647LL && ncoef / 64 < 256LL * 2147483647LL, "jpeg: too many restart intervals or blocks for one launch");
+  TORCH_CHECK(buf.scalar_type() == at::kShort && buf.numel() == ncoef + 16, "jpeg: buf int16 [B * mcus * blocks * 64 + 16]");
+  TORCH_CHECK(chunk >= 16 && chunk % 16 == 0 && chunk < (1LL << 28), "jpeg: chunk bytes a multiple of 16");
+  TORCH_CHECK(threads >= 64 && threads <= 1024 && threads % 64 == 0, "jpeg: 64..1024 lanes per workgroup");
+  TORCH_CHECK(ngroups >= 0 && ngroups <= nivals, "jpeg: at most one group per interval");
+  TORCH_CHECK(nbytes >= 0 && nbytes < 4294967295LL && staged.scalar_type() == at::kByte && extra % 4 == 0 &&
+              extra >= 8 * nivals + nbytes && staged.numel() >= extra + 4 * nivals + 8 * ngroups,
+              "jpeg: staged uint8 [8 * B * intervals + nbytes | 4 * B * intervals + 8 * groups]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(staged.data_ptr()) % 4 == 0 && reinterpret_cast<uintptr_t>(buf.data_ptr()) % 16 == 0,
+              "jpeg: staged 4-byte aligned, buf 16-byte aligned");
+  a.coef = buf.data_ptr<int16_t>();
+  JpegDecodeIn d;
+  d.intervals = reinterpret_cast<const uint32_t*>(staged.data_ptr<uint8_t>());
+  d.bytes = staged.data_ptr<uint8_t>() + 8 * nivals;
+  d.nbytes = (uint32_t)nbytes;
+  d.tables = reinterpret_cast<const uint32_t*>(tables.data_ptr<int>()) + 128 + 544;
+  d.status = reinterpret_cast<unsigned long long*>(a.coef + ncoef);
+  d.zero_bytes = (ncoef + 16) * 2;
+  JpegSyncIn y;
+  y.lane0 = reinterpret_cast<const uint32_t*>(staged.data_ptr<uint8_t>() + extra);
+  y.groups = y.lane0 + nivals;
+  y.ngroups = (int)ngroups;
+  y.cb = (uint32_t)chunk;
+  y.words = reinterpret_cast<uint32_t*>(a.coef + ncoef + 4);
+  launch_jpeg_entropy_decode_chunked(a, d, y, (int)threads, cur_stream());
+}
+
 // PIL's GaussianBlur (blur contract: blur_pil.hip).  img uint8 [H, W, 3]; out uint8 [N, H, W, 3].
 void blur_pil_check(const at::Tensor& img, const at::Tensor& out) {
   CHECK_DEV(img); CHECK_CONTIG(img); CHECK_DEV(out); CHECK_CONTIG(out);
@@ -1091,6 +1140,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("jpeg_write", &jpeg_write, nogil());
   m.def("jpeg_reconstruct", &jpeg_reconstruct, nogil());
   m.def("jpeg_entropy_decode", &jpeg_entropy_decode, nogil());
+  m.def("jpeg_entropy_decode_chunked", &jpeg_entropy_decode_chunked, nogil());
   m.def("timestep_embedding", &timestep_embedding, nogil());
   m.def("gather_add", &gather_add, nogil());
   m.def("concat2", &concat2, nogil());

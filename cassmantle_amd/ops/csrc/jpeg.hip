@@ -113,9 +113,70 @@
 // Kernel: entropy decode, one lane per restart interval like the coder it mirrors, the decode
 // tables (about 4 KiB) in LDS; the coefficient buffer is zeroed first and only non-zero
 // coefficients are stored.
+//
+// THE CHUNKED ENTROPY DECODE CONTRACT (jpeg_format.entropy_decode_chunked is its numpy model,
+// jpeg_entropy_sync.h the lane run): the same coefficients and the same refusals as the ENTROPY
+// DECODE CONTRACT, with one lane per fixed-size byte chunk of an interval instead of one per
+// interval.  A Huffman decoder started at a wrong position falls into step with the true decode
+// after a short stretch, so lanes start on guesses and iterate until every lane's start equals
+// its predecessor's exit.
+//
+//   Chunks.  The raw bytes of every interval (stuffed zeros included) are cut into chunks of cb
+//   bytes, the last one shorter; chunks never cross an interval.  cb = the smallest multiple of
+//   16 that is >= chunk_bytes (itself >= 16) and leaves the longest interval of the call at most
+//   1024 chunks.  An interval is shorter than 2^28 bytes (bit positions are 32-bit words).  A
+//   symbol is at most 27 bits = 5 data bytes = 10 raw bytes, so an exit lies less than 16 bytes
+//   past the chunk end: inside the next chunk's cb, and a 7-bit offset from the chunk end.
+//   State (p, blk, k).  p = raw bit position in the interval of the next symbol's first bit,
+//   never inside a stuffed 0x00; blk = the block of the MCU it belongs to (selects luma / chroma
+//   tables as in jpeg_decode_interval); k = 0: a DC symbol is next, else the zig-zag index of the
+//   AC symbol.  A symbol is a code word plus its value bits; a ZRL is a symbol.
+//   Lane run.  From its start a lane decodes symbols while p is before its chunk's end, with the
+//   structural rules above (TRUNCATED, BAD_CODE, OVERRUN; a 0xFF not followed by 0x00 ends the
+//   data), no predictor and no WIDE rule.  It counts the DC symbols it decoded (blocks started)
+//   and exits in the state at the first symbol boundary at or past the chunk end, or in "error"
+//   (the last lane of an interval runs to the interval's end and normally ends in TRUNCATED
+//   inside the padding).  What a lane makes of bytes behind the end of the data is left open
+//   (the kernel decodes them like any others, the numpy model stops with TRUNCATED): no valid
+//   chain reaches them, because a symbol that needs bits from there is TRUNCATED.
+//   Rounds (Jacobi).  Round 0: lane 0 of an interval starts at (0, 0, 0), lane c > 0 at (first
+//   bit of its chunk, 0, 0), one byte later when the chunk's first byte is a stuffed zero (the
+//   byte before it in the interval is 0xFF).  Round r + 1: a lane whose predecessor's round-r
+//   exit is a state other than its own start adopts it and runs again; every other lane rests.
+//   The iteration ends with the first round in which no lane runs; `rounds` counts the rounds in
+//   which one did (the largest count of any interval of the call).  Lane c is final after round
+//   c, so rounds <= chunks of the longest interval, and the loop is bounded by that.
+//   Valid chain.  Lane 0 is valid; lane c is valid if lane c - 1 is valid and exited in a state
+//   (after convergence lane c's start).  The valid lanes' runs, in order, are the serial decode.
+//   Placement.  The exclusive scan of the valid lanes' block counts over the interval is the
+//   index of the first block a lane starts (a lane that starts inside a block, k != 0, continues
+//   the block before it).  Blocks at or past the interval's block count are dropped, and so are
+//   errors in them: the serial decoder never looks past its last block.
+//   Write pass.  Valid lanes run once more and store into the zeroed buffer: the DC difference at
+//   coefficient 0, non-zero AC values at their k; every store index is checked.  They count the
+//   blocks inside the image they completed.
+//   DC pass.  Per interval and component an inclusive 32-bit prefix sum of the DC differences in
+//   block order replaces them.  A predictor with |predictor * Q| > T is not stored (never
+//   truncated to 16 bits) and raises the flag.  The first such predictor in block order is below
+//   T + 2^11 in magnitude, so a wrapped sum cannot hide it.
+//   Check pass.  One thread per block: |coefficient * Q| <= T for all 64 and sum d^2 <= T^2.
+//   Flag.  Raised by a structural error of a valid lane in a block inside the image, by the DC
+//   and check passes, by an interval outside the staged bytes; and the call counts as flagged
+//   when the valid lanes completed fewer blocks than the image has.
+//   Refusals are the serial decoder's.  A flagged call zeroes the buffer and runs
+//   jpeg_entropy_decode_kernel on the same staged bytes; its status decides what is raised (and
+//   were it OK, its coefficients would be used).  The chunked path guarantees: serial OK => no
+//   flag and equal coefficients; serial error => flag.
+//
+// Kernels: sync (one workgroup of up to 1024 lanes per group of consecutive intervals of one
+// image holding at most 1024 chunks; decode tables, packed exits and the scans in LDS; rounds
+// separated by block-uniform barriers; validity and block scans, then the write pass) -> DC
+// prefix (one workgroup per interval) -> check (one thread per block).  The host cuts the groups
+// and stages them with the bytes.
 #include "common.h"
 #include "kernels.h"
 #include "jpeg_entropy_dec.h"
+#include "jpeg_entropy_sync.h"
 
 namespace {
 
@@ -599,6 +660,188 @@ __global__ __launch_bounds__(64) void jpeg_entropy_decode_kernel(JpegArgs a, Jpe
     atomicMax(d.status, ((unsigned long long)(0xffffffffu - (uint32_t)gid) << 32) | (unsigned long long)st);
 }
 
+// ---------------------------------------------------------------------------------- chunked entropy decode
+// Inclusive scan of one word per thread over the block (Hillis-Steele, buf = 2 * N words of LDS).
+// Every thread of the block calls it; the barriers are block-uniform.
+template <int N>
+CM_DEVICE uint32_t jpeg_block_scan(uint32_t v, uint32_t* buf) {
+  const int t = threadIdx.x, n = blockDim.x;
+  int cur = 0;
+  buf[t] = v;
+  __syncthreads();
+  for (int dlt = 1; dlt < n; dlt <<= 1) {
+    uint32_t x = buf[cur * N + t];
+    if (t >= dlt) x += buf[cur * N + t - dlt];
+    buf[(cur ^ 1) * N + t] = x;
+    __syncthreads();
+    cur ^= 1;
+  }
+  const uint32_t r = buf[cur * N + t];
+  __syncthreads();                     // buf is free again
+  return r;
+}
+
+// One lane per chunk, one workgroup per group of consecutive intervals (y.groups).  Thread t is
+// lane t of the group; its interval is the last one whose first lane (y.lane0) is <= t.  Threads
+// past the last chunk stay idle but take every barrier: nothing returns before the last one, and
+// every loop around a barrier has a block-uniform condition (an LDS word read after a barrier,
+// blockDim).
+__global__ __launch_bounds__(JPEG_SYNC_MAX_CHUNKS) void jpeg_entropy_sync_kernel(JpegArgs a, JpegDecodeIn d, JpegSyncIn y) {
+  constexpr int N = JPEG_SYNC_MAX_CHUNKS;
+  __shared__ uint32_t tabs[JPEG_DEC_WORDS];
+  __shared__ uint32_t sl0[N], sexit[N], sbuf[2 * N];
+  __shared__ uint32_t sany[2];
+  const int t = threadIdx.x, n = blockDim.x;
+  for (int i = t; i < JPEG_DEC_WORDS; i += n) tabs[i] = d.tables[i];
+  const long long nivals = (long long)a.B * a.nint;
+  const long long g0 = y.groups[2 * blockIdx.x];
+  uint32_t gn = y.groups[2 * blockIdx.x + 1];
+  if (g0 >= nivals) gn = 0;
+  else if (gn > nivals - g0) gn = (uint32_t)(nivals - g0);
+  if (gn > (uint32_t)N) gn = N;
+  for (uint32_t i = t; i < gn; i += n) sl0[i] = y.lane0[g0 + i];
+  if (t == 0) sany[0] = sany[1] = 0;
+  __syncthreads();
+
+  // this lane's interval and chunk
+  bool active = false;
+  uint32_t l0 = 0, len = 0, begin = 0, end = 0;
+  const uint8_t* bytes = d.bytes;
+  int16_t* coef = a.coef;
+  int nblk = 0;
+  if (gn > 0) {
+    uint32_t lo = 0, hi = gn;
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (sl0[mid] <= (uint32_t)t) lo = mid; else hi = mid;
+    }
+    l0 = sl0[lo];
+    const long long gid = g0 + lo;
+    const int b = (int)(gid / a.nint), it = (int)(gid % a.nint);
+    const int mcus = a.mx * a.my;
+    const long long m0 = (long long)it * a.restart;
+    const uint32_t off = d.intervals[2 * gid], ln = d.intervals[2 * gid + 1];
+    if (l0 <= (uint32_t)t && l0 < (uint32_t)n) {
+      const uint32_t c = (uint32_t)t - l0;
+      const unsigned long long bg = (unsigned long long)c * y.cb;
+      if (m0 >= mcus || off > d.nbytes || ln > d.nbytes - off || ln >= JPEG_SYNC_MAX_LEN) {
+        if (c == 0) atomicOr(y.words, 1u);                     // the serial kernel names the error
+      } else if (bg < ln) {
+        active = true;
+        len = ln;
+        begin = (uint32_t)bg;
+        end = (uint32_t)min((unsigned long long)ln, bg + y.cb);
+        bytes = d.bytes + off;
+        nblk = (int)min((long long)a.restart, mcus - m0) * a.nb;
+        coef = a.coef + ((long long)b * mcus + m0) * a.nb * 64;
+      }
+    }
+  }
+  const bool head = begin == 0;          // lane 0 of its interval: its start is the truth
+  uint32_t start = active && !head ? jpeg_sync_pack(jpeg_sync_guess(bytes, len, begin), 0, 0, begin) : 0u;
+  uint32_t blocks = 0;
+  bool run = active;
+  sexit[t] = JPEG_SYNC_ERR;
+  if (run) sany[0] = 1;
+  __syncthreads();
+
+  // the rounds
+  int rounds = 0;
+  for (int r = 0; r < n && sany[r & 1] != 0; ++r) {
+    ++rounds;
+    if (run) {
+      JpegSyncRun s;
+      jpeg_sync_unpack(start, begin, s);
+      jpeg_sync_lane_run<false>(bytes, len, end, tabs, a.nb, s, 0, 0, nullptr);
+      blocks = s.blocks;
+      sexit[t] = s.err != JPEG_DEC_OK ? JPEG_SYNC_ERR : jpeg_sync_pack(s.p, s.blk, s.k, end);
+    }
+    if (t == 0) sany[(r + 1) & 1] = 0;
+    __syncthreads();
+    run = false;
+    if (active && !head) {
+      const uint32_t e = sexit[t - 1];                         // !head: t > l0 >= 0
+      if (e != JPEG_SYNC_ERR && e != start) {
+        start = e;
+        run = true;
+        sany[(r + 1) & 1] = 1;
+      }
+    }
+    __syncthreads();
+  }
+
+  // valid chain: no error exit among the lanes before this one in its interval
+  const uint32_t bad = active && sexit[t] == JPEG_SYNC_ERR ? 1u : 0u;
+  const uint32_t badx = jpeg_block_scan<N>(bad, sbuf) - bad;
+  sl0[t] = badx;                                                // the group's lane0 table is no longer needed
+  __syncthreads();
+  const bool valid = active && badx == sl0[l0];
+  __syncthreads();
+  // placement: exclusive scan of the valid lanes' block counts within the interval
+  const uint32_t cnt = valid ? blocks : 0u;
+  const uint32_t cntx = jpeg_block_scan<N>(cnt, sbuf) - cnt;
+  sl0[t] = cntx;
+  __syncthreads();
+  if (valid) {
+    JpegSyncRun s;
+    jpeg_sync_unpack(start, begin, s);
+    const long long first = (long long)(cntx - sl0[l0]) - (s.k != 0 ? 1 : 0);
+    if (first < nblk) {
+      jpeg_sync_lane_run<true>(bytes, len, end, tabs, a.nb, s, (int)first, nblk, coef);
+      if (s.err != JPEG_DEC_OK && s.err_block < nblk) atomicOr(y.words, 1u);
+      if (s.done != 0) atomicAdd(y.words + 2, s.done);
+    }
+  }
+  if (t == 0) atomicMax(y.words + 1, (uint32_t)rounds);
+}
+
+// One workgroup per interval (64 .. 1024 threads, as many as the interval has luma blocks): the DC
+// differences the write pass stored become the predictors.  A thread owns a run of consecutive
+// blocks of the component; its loads are independent, the chain between threads is the scan.
+__global__ __launch_bounds__(1024) void jpeg_dc_prefix_kernel(JpegArgs a, JpegDecodeIn d, JpegSyncIn y) {
+  __shared__ uint32_t sbuf[2 * 1024];
+  const int t = threadIdx.x, n = blockDim.x;
+  const long long gid = blockIdx.x;
+  const int b = (int)(gid / a.nint), it = (int)(gid % a.nint);
+  const int mcus = a.mx * a.my;
+  const long long m0 = (long long)it * a.restart;
+  if (m0 >= mcus) return;                                       // the whole block: before any barrier
+  const int nmcu = (int)min((long long)a.restart, mcus - m0), nb = a.nb;
+  int16_t* coef = a.coef + ((long long)b * mcus + m0) * nb * 64;
+  for (int comp = 0; comp < 3; ++comp) {
+    const int per_mcu = comp == 0 ? nb - 2 : 1;
+    const int cnt = nmcu * per_mcu, per = (cnt + n - 1) / n;
+    const int lo = min(cnt, t * per), hi = min(cnt, lo + per);
+    const uint32_t q0 = d.tables[comp == 0 ? 0 : 64];
+    uint32_t sum = 0;
+    for (int i = lo; i < hi; ++i) {
+      const long long blk = (long long)(i / per_mcu) * nb + (comp == 0 ? i % per_mcu : nb - 3 + comp);
+      sum += (uint32_t)(int)coef[blk * 64];
+    }
+    uint32_t pred = jpeg_block_scan<1024>(sum, sbuf) - sum;
+    bool wide = false;
+    for (int i = lo; i < hi; ++i) {
+      const long long blk = (long long)(i / per_mcu) * nb + (comp == 0 ? i % per_mcu : nb - 3 + comp);
+      pred += (uint32_t)(int)coef[blk * 64];
+      const bool ok = jpeg_sync_dc_ok(pred, q0);
+      coef[blk * 64] = ok ? (int16_t)(int32_t)pred : (int16_t)0;
+      wide |= !ok;
+    }
+    if (wide) atomicOr(y.words, 1u);
+  }
+}
+
+// One thread per block: the refusal rule on what was stored.
+__global__ __launch_bounds__(256) void jpeg_block_check_kernel(JpegArgs a, JpegDecodeIn d, JpegSyncIn y) {
+  __shared__ uint32_t q[JPEG_DEC_QZ_WORDS];
+  if (threadIdx.x < JPEG_DEC_QZ_WORDS) q[threadIdx.x] = d.tables[threadIdx.x];
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)a.B * a.mx * a.my * a.nb) return;
+  const int blk = (int)(i % a.nb);
+  if (!jpeg_sync_block_ok(a.coef + i * 64, q + (blk < a.nb - 2 ? 0 : 64))) atomicOr(y.words, 1u);
+}
+
 }  // namespace
 
 void launch_jpeg_count(const JpegArgs& a, hipStream_t s) {
@@ -635,4 +878,16 @@ void launch_jpeg_entropy_decode(const JpegArgs& a, const JpegDecodeIn& d, hipStr
   launch_zero(a.coef, d.zero_bytes, s);
   const unsigned eg = (unsigned)(((long long)a.B * a.nint + 63) / 64);
   hipLaunchKernelGGL(jpeg_entropy_decode_kernel, dim3(eg), dim3(64), 0, s, a, d);
+}
+
+void launch_jpeg_entropy_decode_chunked(const JpegArgs& a, const JpegDecodeIn& d, const JpegSyncIn& y, int threads,
+                                        hipStream_t s) {
+  launch_zero(a.coef, d.zero_bytes, s);
+  if (y.ngroups > 0)
+    hipLaunchKernelGGL(jpeg_entropy_sync_kernel, dim3(y.ngroups), dim3(threads), 0, s, a, d, y);
+  const int luma = min(a.restart, a.mx * a.my) * (a.nb - 2);
+  const int dct = min(1024, (luma + 63) / 64 * 64);
+  hipLaunchKernelGGL(jpeg_dc_prefix_kernel, dim3((unsigned)((long long)a.B * a.nint)), dim3(dct), 0, s, a, d, y);
+  const unsigned cg = (unsigned)(((long long)a.B * a.mx * a.my * a.nb + 255) / 256);
+  hipLaunchKernelGGL(jpeg_block_check_kernel, dim3(cg), dim3(256), 0, s, a, d, y);
 }

@@ -250,6 +250,19 @@ struct JpegDecodeIn {
 // zeroes coef and status, then one lane per interval: fills coef (reads B, nb, mx, my, restart,
 // nint, coef of a; restart = MCUs per interval, all of them without DRI)
 void launch_jpeg_entropy_decode(const JpegArgs& a, const JpegDecodeIn& d, hipStream_t s);
+// chunked entropy decode (chunked entropy decode contract in jpeg.hip's header comment; jpeg_entropy_sync.h)
+struct JpegSyncIn {
+  const uint32_t* lane0 = nullptr;       // [B][nint] the interval's first lane within its group
+  const uint32_t* groups = nullptr;      // [ngroups][2] (first interval gid, intervals): one image, at most 1024 chunks
+  int ngroups = 0;
+  uint32_t cb = 0;                       // chunk bytes, a multiple of 16
+  uint32_t* words = nullptr;             // [4] flag, rounds, blocks completed, unused: behind the status word, zeroed with it
+};
+// zeroes coef, status and words, then sync (one lane per chunk, `threads` a multiple of 64 that
+// covers the largest group), DC prefix and check: fills coef unless words[0] is raised or
+// words[2] is below the block count
+void launch_jpeg_entropy_decode_chunked(const JpegArgs& a, const JpegDecodeIn& d, const JpegSyncIn& y, int threads,
+                                        hipStream_t s);
 
 // PIL's GaussianBlur, bit for bit (blur_pil.hip; blur contract in its header comment)
 int blur_pil_max_tiled_radius();

@@ -836,6 +836,216 @@ def entropy_decode(stream: JpegStream, first_interval: int = 0) -> np.ndarray:
     return out
 
 
+# ----------------------------------------------------------------------------- chunked entropy decode contract
+# The same coefficients from one lane per fixed-size byte chunk: the CHUNKED ENTROPY DECODE CONTRACT
+# section of jpeg.hip's header comment; ops/csrc/jpeg_entropy_sync.h is the lane run the kernel and
+# the host program compile.
+SYNC_MAX_CHUNKS = 1024                 # chunks per interval, lanes per workgroup
+SYNC_MAX_LEN = 1 << 28                 # bytes per interval: raw bit positions are 32-bit words
+
+
+def chunk_bytes_for(longest: int, chunk_bytes: int = 32) -> int:
+    """The effective chunk size: the smallest multiple of 16 that is >= ``chunk_bytes`` and cuts an
+    interval of ``longest`` bytes into at most SYNC_MAX_CHUNKS chunks."""
+    if int(chunk_bytes) != chunk_bytes or chunk_bytes < 16:
+        raise ValueError("jpeg: chunk_bytes must be an integer >= 16")
+    need = (longest + SYNC_MAX_CHUNKS - 1) // SYNC_MAX_CHUNKS
+    return (max(int(chunk_bytes), need, 16) + 15) // 16 * 16
+
+
+class _SyncInterval:
+    """One interval for the lane runs: the unstuffed data and both maps between raw and data bytes."""
+
+    def __init__(self, raw: bytes, books, nb: int) -> None:
+        self.nb, self.books, self.n = nb, books, len(raw)
+        a = np.frombuffer(raw, dtype=np.uint8)
+        ff = np.flatnonzero(a == 0xFF)
+        nxt = np.append(a, 1)[ff + 1]          # a 0xFF that ends the interval is stray too
+        stray = ff[nxt != 0]
+        end = int(stray[0]) if stray.size else len(raw)
+        keep = np.ones(end, dtype=bool)
+        keep[ff[ff < end] + 1] = False           # the stuffed zeros (all inside [0, end): nxt == 0 there)
+        self.rawidx = np.append(np.flatnonzero(keep), end).tolist()      # data byte -> raw byte; [-1] = the data's end
+        didx = np.full(len(raw) + 1, -1, dtype=np.int64)
+        didx[self.rawidx] = np.arange(len(self.rawidx))
+        self.dataidx = didx.tolist()             # raw byte -> data byte, -1: a stuffed zero or past the data
+        self.buf = a[:end][keep].tobytes()
+        self.raw = raw
+
+    def guess(self, begin: int) -> int:
+        stuffed = 0 < begin < self.n and self.raw[begin] == 0 and self.raw[begin - 1] == 0xFF
+        return 8 * (begin + (1 if stuffed else 0))
+
+    def run(self, state, end: int, out=None, first: int = 0):
+        """Symbols from ``state`` = (raw bit, blk, k) while the position is before raw byte ``end``.
+        -> (exit state or None, blocks started, blocks completed inside ``out``, error, its block).
+        A start that is no data position (past a stray 0xFF) is TRUNCATED at once."""
+        p, blk, k = state
+        buf, nbits, rawidx, nb = self.buf, 8 * len(self.buf), self.rawidx, self.nb
+        blocks = done = 0
+        g = first
+        nblk = len(out) if out is not None else 0
+        if p >= 8 * end:
+            return state, 0, 0, OK, 0
+        di = self.dataidx[p >> 3]
+        if di < 0:
+            return None, 0, 0, TRUNCATED, g
+        pd = 8 * di + (p & 7)
+
+        def bits(at: int, n: int) -> int:
+            i = at >> 3
+            v = int.from_bytes(buf[i: i + 5].ljust(5, b"\0"), "big")
+            return (v >> (40 - (at & 7) - n)) & ((1 << n) - 1)
+
+        def symbol(book, at: int):
+            left = nbits - at
+            w = bits(at, 16)
+            hit = book[0][w >> 8]
+            if hit:
+                length, sym = hit
+            else:
+                for length in range(9, 17):
+                    sym = book[length].get(w >> (16 - length))
+                    if sym is not None:
+                        break
+                else:
+                    return -(TRUNCATED if left < 16 else BAD_CODE), 0
+            if length > left:
+                return -TRUNCATED, 0
+            return sym, length
+        while rawidx[pd >> 3] < end:
+            tc = 0 if blk < nb - 2 else 1
+            complete = False
+            v = 0
+            if k == 0:
+                s, used = symbol(self.books[tc], pd)
+                if s < 0:
+                    return None, blocks, done, -s, g
+                if s > 11:
+                    return None, blocks, done, BAD_CODE, g
+                if s:
+                    if used + s > nbits - pd:
+                        return None, blocks, done, TRUNCATED, g
+                    v = bits(pd + used, s)
+                    v = v if v >= (1 << (s - 1)) else v - (1 << s) + 1
+                    used += s
+                blocks += 1
+                if v and 0 <= g < nblk:
+                    out[g, 0] = v
+                k = 1
+            else:
+                rs, used = symbol(self.books[2 + tc], pd)
+                if rs < 0:
+                    return None, blocks, done, -rs, g
+                r, s = rs >> 4, rs & 15
+                if s == 0:
+                    if rs == 0:
+                        complete = True
+                    elif r != 15:
+                        return None, blocks, done, BAD_CODE, g
+                    elif k + 16 > 63:
+                        return None, blocks, done, OVERRUN, g
+                    else:
+                        k += 16
+                elif s > 10:
+                    return None, blocks, done, BAD_CODE, g
+                elif k + r > 63:
+                    return None, blocks, done, OVERRUN, g
+                elif used + s > nbits - pd:
+                    return None, blocks, done, TRUNCATED, g
+                else:
+                    v = bits(pd + used, s)
+                    v = v if v >= (1 << (s - 1)) else v - (1 << s) + 1
+                    used += s
+                    k += r
+                    if 0 <= g < nblk:
+                        out[g, k] = v
+                    k += 1
+                    complete = k > 63
+            if complete:
+                if 0 <= g < nblk:
+                    done += 1
+                g += 1
+                k = 0
+                blk = 0 if blk + 1 == nb else blk + 1
+            pd += used
+        return (8 * rawidx[pd >> 3] + (pd & 7), blk, k), blocks, done, OK, 0
+
+
+def entropy_decode_chunked(stream: JpegStream, chunk_bytes: int = 32, first_interval: int = 0,
+                           stats: dict = None) -> np.ndarray:
+    """What :func:`entropy_decode` returns, and raises, computed the way the CHUNKED ENTROPY DECODE
+    CONTRACT says: one lane per chunk, Jacobi rounds until every lane starts where its predecessor
+    ended, valid chain, placement, write pass, DC prefix sums, check pass; a flagged stream is
+    handed to :func:`entropy_decode`, whose verdict stands.  ``stats`` receives ``chunks`` (all
+    intervals), ``rounds`` (the largest of any interval), ``lane_runs``, ``chunk_bytes`` (the
+    effective value) and ``serial_fallback``."""
+    _, nb, mx, my = geometry(stream.H, stream.W, stream.sampling)
+    mcus = mx * my
+    per = stream.restart or mcus
+    longest = max(ln for _, ln in stream.intervals)
+    cb = chunk_bytes_for(longest, chunk_bytes)
+    if longest >= SYNC_MAX_LEN:
+        raise JpegUnsupported("jpeg: a restart interval of 2^28 bytes or more")
+    books = [_codebook(b, v) for b, v in stream.huff]
+    qz = np.asarray([[t[ZIGZAG[z]] for z in range(64)] for t in stream.qtables], dtype=np.int64)
+    work = np.zeros((mcus * nb, 64), dtype=np.int64)
+    chunks = rounds = lane_runs = completed = 0
+    flag = False
+    for it, (off, ln) in enumerate(stream.intervals):
+        m0 = it * per
+        nblk = min(per, mcus - m0) * nb
+        out = work[m0 * nb: m0 * nb + nblk]
+        n = (ln + cb - 1) // cb
+        chunks += n
+        if n == 0:
+            continue
+        iv = _SyncInterval(stream.data[off: off + ln], books, nb)
+        ends = [min(ln, (c + 1) * cb) for c in range(n)]
+        starts = [(0, 0, 0)] + [(iv.guess(c * cb), 0, 0) for c in range(1, n)]
+        exits, counts = [None] * n, [0] * n
+        run, r = list(range(n)), 0
+        while run and r < n:                   # lane c is final after round c
+            r += 1
+            lane_runs += len(run)
+            for c in run:
+                exits[c], counts[c] = iv.run(starts[c], ends[c])[:2]
+            nxt = []
+            for c in run:
+                if c + 1 < n and exits[c] is not None and exits[c] != starts[c + 1]:
+                    starts[c + 1] = exits[c]
+                    nxt.append(c + 1)
+            run = nxt
+        rounds = max(rounds, r)
+        first = 0
+        for c in range(n):                      # the valid chain, in order
+            if c and exits[c - 1] is None:
+                break
+            at = first - (1 if starts[c][2] else 0)
+            if at < nblk:
+                _, _, done, err, where = iv.run(starts[c], ends[c], out, at)
+                completed += done
+                flag |= err != OK and where < nblk
+            first += counts[c]
+        # DC pass: 32-bit inclusive prefix sums per component, a failing predictor is not stored
+        blk = np.arange(nblk) % nb
+        for comp in range(3):
+            sel = np.flatnonzero(blk < nb - 2 if comp == 0 else blk == nb - 3 + comp)
+            pred = (np.cumsum(out[sel, 0]) + 2 ** 31) % 2 ** 32 - 2 ** 31
+            ok = np.abs(pred) <= WIDE_T // int(qz[min(comp, 1), 0])
+            flag |= not bool(ok.all())
+            out[sel, 0] = np.where(ok, pred, 0)
+    # check pass
+    d = work * qz[(np.arange(mcus * nb) % nb >= nb - 2).astype(np.int64)]
+    flag |= bool((np.abs(d) > WIDE_T).any() or ((d * d).sum(-1) > WIDE_T * WIDE_T).any())
+    flag |= completed < mcus * nb
+    if stats is not None:
+        stats.update(chunks=chunks, rounds=rounds, lane_runs=lane_runs, chunk_bytes=cb, serial_fallback=bool(flag))
+    if flag:
+        return entropy_decode(stream, first_interval)
+    return work.reshape(mcus, nb, 64).astype(np.int16)
+
+
 def jpeg_decode(data) -> np.ndarray:
     """Baseline JPEG bytes -> uint8 [H, W, 3], the pixels a libjpeg decoder (PIL) returns for them:
     ``reconstruct(entropy_decode(parse(data)))`` with the stream's own quantisation tables."""

@@ -188,7 +188,9 @@ def build_jpeg_decode_fn(cfg: Config, device: Optional[str] = None):
     DeviceImage``, one ops.jpeg_decode call on the calling thread's current stream, PIL's pixels
     bit for bit.  ``fn`` returns ``None``, which leaves the stream to PIL on the host as without
     the flag, for a stream with fewer than ``jpeg_decode_min_intervals`` restart intervals and for
-    bytes the decoder refuses (outside its scope, or malformed).  ``None`` unless
+    bytes the decoder refuses (outside its scope, or malformed).  With ``jpeg_decode_chunked`` a
+    stream under that interval count is decoded too, in chunks of ``jpeg_decode_chunk_bytes``
+    (``mode="chunked"``), and only a refused one returns ``None``.  ``None`` unless
     ``gpu_jpeg_decode`` and ``gpu_blur`` are set and the device is a GPU."""
     dev = device or ("cuda" if torch.cuda.is_available() else "cpu")
     m = cfg.model
@@ -202,7 +204,10 @@ def build_jpeg_decode_fn(cfg: Config, device: Optional[str] = None):
         try:
             stream = jf.parse(jpeg)
             if len(stream.intervals) < m.jpeg_decode_min_intervals:
-                return None
+                if not m.jpeg_decode_chunked:
+                    return None
+                return DeviceImage(ops.jpeg_decode(stream, device=dev, mode="chunked",
+                                                   chunk_bytes=m.jpeg_decode_chunk_bytes))
             return DeviceImage(ops.jpeg_decode(stream, device=dev))
         except (jf.JpegUnsupported, jf.JpegError):
             return None

@@ -42,7 +42,11 @@ decoded in HBM), each timed to a device synchronise, interleaved ``--reps`` time
 of each.  Streams: the GPU encoder's content JPEG at one MCU row, 16 and 4 MCUs per restart
 interval, and a PIL-encoded stream without restart markers (one lane decodes the whole image).
 Per record: host wall time, CPU time, bytes moved host to device, and per stream the device time
-(HIP events) of the zero + entropy decode launch and of the zero alone.
+(HIP events) of the zero + entropy decode launch and of the zero alone.  The same streams again
+through ``ops.jpeg_decode(mode="chunked")`` (``jpeg_decode_chunked``) at 16, 32, 64 and 128 bytes
+per chunk, with the rounds and chunks of every call and the device time of the chunked launch
+alone; and one more image, the worst case of that path: 512 x 512 noise (``tests/jpeg_cases.py``),
+PIL-encoded at quality 75 without restart markers.
 
     python tools/bench_jpeg.py --decode [--res 512 1024] [--reps 2] [--out profiles/jpeg_decode.jsonl]
 """
@@ -56,6 +60,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 MAX_BLUR, BUCKET, QUALITY = 15.0, 0.25, 75
+CHUNKS = (16, 32, 64, 128)        # --decode: the chunk sizes of the chunked entropy decode rows
 
 
 def source_image(res: int):
@@ -310,13 +315,40 @@ def decode_main(a, emit) -> int:
             best = [min(best[0], ev[0].elapsed_time(ev[1])), min(best[1], ev[1].elapsed_time(ev[2]))]
         return best
 
-    for res in a.res:
-        img = source_image(res).copy()
+    def chunked_device_ms(stream, chunk: int, iters: int = 5) -> float:
+        """device time in ms of the chunked launch alone (zero, sync + write, DC prefix, check), HIP events"""
+        _, nb, mx, my = jf.geometry(stream.H, stream.W, stream.sampling)
+        lens = np.asarray([[ln for _, ln in stream.intervals]], dtype=np.int64)
+        cb = jf.chunk_bytes_for(int(lens.max()), chunk)
+        lane0, groups, threads, _ = ops._jpeg_chunk_groups(lens, cb)
+        staged, base, tables, extra = ops._jpeg_decode_inputs([stream], torch.device("cuda"),
+                                                              np.concatenate([lane0, groups.reshape(-1)]))
+        buf = torch.empty(mx * my * nb * 64 + 16, device="cuda", dtype=torch.int16)
+        best = 1e9
+        for _ in range(iters + 1):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            torch.cuda.synchronize()
+            ev[0].record()
+            ext().jpeg_entropy_decode_chunked(staged, base, tables, buf, 1, stream.H, stream.W,
+                                              int(stream.sampling == "420"), stream.restart, extra, len(groups), cb,
+                                              threads)
+            ev[1].record()
+            torch.cuda.synchronize()
+            best = min(best, ev[0].elapsed_time(ev[1]))
+        return best
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import jpeg_cases as jc
+    # the resolutions asked for, then the worst case for the chunked path: noise (long blocks)
+    for res, kind in [(r, "background") for r in a.res] + [(512, "noise")]:
+        img = source_image(res).copy() if kind == "background" else jc.noise(res, res)
         t = torch.from_numpy(img).cuda()
         mcu_row = (res + 15) // 16
-        streams = {f"in-tree, {r} MCUs per interval" + (" (one MCU row)" if r == mcu_row else ""):
-                   ops.jpeg_encode(t, QUALITY, "420", r)[0] for r in (mcu_row, 16, 4)}
-        streams["PIL, no DRI (one interval)"] = encode_jpeg(img, QUALITY)
+        streams = {}
+        if kind == "background":
+            streams = {f"in-tree, {r} MCUs per interval" + (" (one MCU row)" if r == mcu_row else ""):
+                       ops.jpeg_encode(t, QUALITY, "420", r)[0] for r in (mcu_row, 16, 4)}
+        streams["PIL, no DRI (one interval)" + ("" if kind == "background" else ", noise")] = encode_jpeg(img, QUALITY)
         for name, jpeg in streams.items():
             st = jf.parse(jpeg)
             staged_bytes = 8 * len(st.intervals) + st.intervals[-1][0] + st.intervals[-1][1] - st.scan_offset
@@ -341,12 +373,30 @@ def decode_main(a, emit) -> int:
                            "jpeg_bytes": len(jpeg), "wall_ms": round(wall * 1e3, 3), "cpu_ms": round(cpu * 1e3, 3),
                            "h2d_bytes": (staged_bytes + 15) // 16 * 16}
 
+            def run_chunked(chunk):
+                info = {}
+                torch.cuda.synchronize()
+                w0, c0 = time.perf_counter(), time.process_time()
+                x = ops.jpeg_decode(jpeg, device="cuda", mode="chunked", chunk_bytes=chunk, info=info)
+                torch.cuda.synchronize()
+                wall, cpu = time.perf_counter() - w0, time.process_time() - c0
+                return x, dict(info, res=res, stream=name, path=f"ops.jpeg_decode(mode=chunked, {chunk})",
+                               intervals=len(st.intervals), jpeg_bytes=len(jpeg), wall_ms=round(wall * 1e3, 3),
+                               cpu_ms=round(cpu * 1e3, 3))
+
             xp, _ = run_parent()
             xn, _ = run_new()
             equal = bool(torch.equal(xp, xn))
+            equal_chunked = {c: bool(torch.equal(xp, run_chunked(c)[0])) for c in CHUNKS}
             for rep in range(a.reps):
                 emit(dict(run_parent()[1], rep=rep))
                 emit(dict(run_new()[1], rep=rep, equals_pil_decode=equal))
+                for c in CHUNKS:
+                    emit(dict(run_chunked(c)[1], rep=rep, equals_pil_decode=equal_chunked[c]))
+            for c in CHUNKS:
+                emit({"res": res, "stream": name, "intervals": len(st.intervals), "chunk_bytes_asked": c,
+                      "chunked_launch_device_ms": round(chunked_device_ms(st, c), 4),
+                      "kernels": "zero_kernel + jpeg_entropy_sync_kernel + jpeg_dc_prefix_kernel + jpeg_block_check_kernel"})
             both, zero = entropy_device_ms(st)
             emit({"res": res, "stream": name, "intervals": len(st.intervals),
                   "zero_plus_entropy_decode_device_ms": round(both, 4), "zero_alone_device_ms": round(zero, 4),
