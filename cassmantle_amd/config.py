@@ -127,7 +127,13 @@ class ModelConfig:
     # MCUs per restart interval, the unit of parallel entropy coding; 0 = one MCU row (W / 16).
     # Shorter intervals code faster but every marker and DC reset costs bytes on these small
     # blurred images (tools/bench_jpeg.py sweep: +16 % / +21 % at 4 MCUs for 512^2 / 1024^2)
+    # -1 = no restart markers at all (what PIL writes, and the smallest stream): needs
+    # jpeg_entropy=block, the interval coder has one lane per interval
     jpeg_restart_mcus: int = 0
+    # the entropy coder of ops.jpeg_encode: interval (one lane per restart interval) | block (one
+    # lane per 8x8 block whatever the interval, the same bytes; profiles/jpeg_block.jsonl).
+    # interval: today's path
+    jpeg_entropy: str = "interval"
     # the content JPEG itself (radius 0, the bytes the content version hashes) encoded on the GPU
     # too, and its DECODED pixels (computed there from the same coefficients) registered as the
     # blur source: the image never crosses to the host, and masked bytes no longer depend on

@@ -843,13 +843,20 @@ def _jpeg_plan(device, H: int, W: int, quality: int, sampling: str, restart_mcus
     return plan
 
 
+JPEG_ENTROPY_CODERS = ("interval", "block")
+
+
 def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: int = 4,
-                return_decoded: bool = False):
+                return_decoded: bool = False, entropy: str = "interval"):
     """Baseline JPEG (JFIF) of uint8 ``[B, H, W, 3]`` / ``[H, W, 3]`` images (a tensor, or a
     ``DeviceImage``): one complete JPEG byte string per image, bit for bit what
     ``ops.reference.jpeg_encode`` writes (the contract: ops/csrc/jpeg.hip).  ``sampling`` "420" |
     "444"; ``restart_mcus`` MCUs per restart interval, the unit of parallel entropy coding (the
-    HIP path needs >= 1; 0 = no restart markers, reference only).
+    HIP path needs >= 1; 0 = no restart markers, reference only) with ``entropy="interval"``.
+    ``entropy="block"``: the block-parallel entropy coder (ops/csrc/jpeg.hip), one lane per 8x8
+    block whatever the restart interval, the same bytes; it accepts ``restart_mcus >= 0``, so it
+    writes a stream without restart markers (what PIL writes, and the smallest) on the device.
+    Any other value is a ``ValueError``; off the HIP path the argument selects nothing.
 
     ``return_decoded``: ``(bytes per image, decoded)`` instead, ``decoded`` the uint8
     ``[B, H, W, 3]`` pixels a libjpeg decoder (PIL) gives for those bytes, bit for bit
@@ -859,7 +866,11 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
     HIP path, all on the current stream: transform + per-interval byte count + scans, one copy of
     the image offsets to the host (the payload size), the write pass, one copy of the payload;
     then, for ``return_decoded``, the inverse DCT of the coefficient buffer the transform filled
-    and the colour pass (queued behind the payload copy: the pixels stay in HBM)."""
+    and the colour pass (queued behind the payload copy: the pixels stay in HBM).  The block
+    coder has the same two copies: its error word rides behind the offsets, its error byte behind
+    the payload."""
+    if entropy not in JPEG_ENTROPY_CODERS:
+        raise ValueError(f"jpeg_encode: entropy must be one of {JPEG_ENTROPY_CODERS}, not {entropy!r}")
     t = getattr(images, "tensor", images)
     if not isinstance(t, torch.Tensor):
         outs = ref.jpeg_encode(images, quality, sampling, restart_mcus)
@@ -875,21 +886,42 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
         return outs, torch.from_numpy(ref.jpeg_decoded(t, quality, sampling)).to(t.device)
     from . import jpeg_format as jf
     quality, restart_mcus = int(quality), int(restart_mcus)
-    if restart_mcus < 1:
+    if entropy == "interval" and restart_mcus < 1:
         raise ValueError("jpeg_encode: the HIP encoder codes restart intervals in parallel: restart_mcus >= 1")
+    if restart_mcus < 0:
+        raise ValueError("jpeg_encode: restart_mcus >= 0")
     B, H, W, _ = t.shape
     _, nb, mx, my = jf.geometry(H, W, sampling)
     tables, header = _jpeg_plan(t.device, H, W, quality, sampling, restart_mcus)
     t = t.contiguous()
-    nint = (mx * my + restart_mcus - 1) // restart_mcus
+    per = min(restart_mcus, mx * my) if restart_mcus else mx * my          # MCUs per interval
+    nint = (mx * my + per - 1) // per
     coef = torch.empty((B, mx * my, nb, 64), device=t.device, dtype=torch.int16)
-    work = torch.empty(2 * B * nint + B + 1, device=t.device, dtype=torch.int32)
     s420 = int(sampling == "420")
-    ext().jpeg_count(t, tables, header, coef, work, s420, restart_mcus)
-    base = work[: B + 1].cpu().tolist()               # device-to-host copy 1: the image offsets
-    out = torch.empty(base[-1], device=t.device, dtype=torch.uint8)
-    ext().jpeg_write(t, tables, header, coef, work, s420, restart_mcus, out, base[-1])
-    mv = memoryview(out.cpu().numpy())                # device-to-host copy 2: the payload
+    if entropy == "block":
+        # an interval's unstuffed string has a slot for the worst case of every block; only the
+        # words blocks start in are zeroed (by the scan pass), nothing here
+        stride = (per * nb * jf.block_bits_bound() + 31) // 32
+        work = torch.empty(2 * B * nint + B + 2, device=t.device, dtype=torch.int32)
+        blk = torch.empty(B * mx * my * nb + B * nint, device=t.device, dtype=torch.int32)
+        scratch = torch.empty(B * nint * stride, device=t.device, dtype=torch.int32)
+        ext().jpeg_count_blocks(t, tables, header, coef, work, blk, scratch, stride, s420, restart_mcus)
+        base = work[: B + 2].cpu().tolist()           # device-to-host copy 1: the image offsets + the error word
+        if base.pop():
+            raise RuntimeError("jpeg_encode: the block coder refused a scratch index (a block over the bits bound)")
+        out = torch.empty(base[-1] + 1, device=t.device, dtype=torch.uint8)
+        ext().jpeg_write_blocks(t, tables, header, coef, work, blk, scratch, stride, s420, restart_mcus, out, base[-1])
+        host = out.cpu().numpy()                      # device-to-host copy 2: the payload + the error byte
+        if host[-1]:
+            raise RuntimeError("jpeg_encode: the block coder refused a payload index")
+        mv = memoryview(host)
+    else:
+        work = torch.empty(2 * B * nint + B + 1, device=t.device, dtype=torch.int32)
+        ext().jpeg_count(t, tables, header, coef, work, s420, restart_mcus)
+        base = work[: B + 1].cpu().tolist()               # device-to-host copy 1: the image offsets
+        out = torch.empty(base[-1], device=t.device, dtype=torch.uint8)
+        ext().jpeg_write(t, tables, header, coef, work, s420, restart_mcus, out, base[-1])
+        mv = memoryview(out.cpu().numpy())                # device-to-host copy 2: the payload
     outs = [bytes(mv[base[i]: base[i + 1]]) for i in range(B)]
     if not return_decoded:
         return outs

@@ -861,15 +861,21 @@ void decode_attention(const at::Tensor& q, const at::Tensor& k_cache, const at::
 
 // Batched JPEG encode, phase 1 / 2 (ops.jpeg_encode allocates: the payload size is known only
 // after phase 1's offsets reach the host).  tables: int32 [128 + 544] = quantisation | Huffman.
+// blocks: the block-parallel coder's call: restart 0 = no restart markers (one interval), and work has
+// one more word behind base (the error word)
 JpegArgs jpeg_args(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                   at::Tensor& work, int64_t s420, int64_t restart) {
+                   at::Tensor& work, int64_t s420, int64_t restart, bool blocks = false) {
   CHECK_DEV(images); CHECK_CONTIG(images); CHECK_DEV(tables); CHECK_CONTIG(tables); CHECK_DEV(header);
   CHECK_CONTIG(header); CHECK_DEV(coef); CHECK_CONTIG(coef); CHECK_DEV(work); CHECK_CONTIG(work);
   TORCH_CHECK(images.scalar_type() == at::kByte && images.dim() == 4 && images.size(3) == 3 && images.numel() > 0,
               "jpeg: images uint8 [B, H, W, 3]");
   TORCH_CHECK(tables.scalar_type() == at::kInt && tables.numel() == 128 + 544, "jpeg: tables int32 [672]");
   TORCH_CHECK(header.scalar_type() == at::kByte && header.numel() > 0, "jpeg: header uint8");
-  TORCH_CHECK(restart >= 1 && restart < 65536, "jpeg: the HIP encoder needs 1 <= restart_mcus <= 65535");
+  if (blocks) {
+    TORCH_CHECK(restart >= 0 && restart < 65536, "jpeg: restart_mcus 0..65535");
+  } else {
+    TORCH_CHECK(restart >= 1 && restart < 65536, "jpeg: the HIP encoder needs 1 <= restart_mcus <= 65535");
+  }
   JpegArgs a;
   a.img = images.data_ptr<uint8_t>();
   a.B = (int)images.size(0); a.H = (int)images.size(1); a.W = (int)images.size(2);
@@ -877,8 +883,9 @@ JpegArgs jpeg_args(const at::Tensor& images, const at::Tensor& tables, const at:
   const int mcu = s420 ? 16 : 8;
   a.nb = s420 ? 6 : 3;
   a.mx = (a.W + mcu - 1) / mcu; a.my = (a.H + mcu - 1) / mcu;
-  a.restart = (int)restart;
   const long long mcus = (long long)a.mx * a.my;
+  if (restart == 0) restart = mcus;                  // blocks only: the whole image is one interval
+  a.restart = (int)restart;
   a.nint = (int)((mcus + restart - 1) / restart);
   a.hdr_len = (int)header.numel();
   // 32-bit payload offsets: bound by the coder's worst case (20 + 63 * 26 bits per block, every
@@ -887,15 +894,61 @@ JpegArgs jpeg_args(const at::Tensor& images, const at::Tensor& tables, const at:
               "jpeg: batch too large for 32-bit payload offsets");
   TORCH_CHECK(coef.scalar_type() == at::kShort && coef.numel() == (long long)a.B * mcus * a.nb * 64,
               "jpeg: coef int16 [B, mcus, blocks, 64]");
-  TORCH_CHECK(work.scalar_type() == at::kInt && work.numel() == 2LL * a.B * a.nint + a.B + 1,
-              "jpeg: work int32 [2 * B * intervals + B + 1]");
+  const int extra = blocks ? 1 : 0;
+  TORCH_CHECK(work.scalar_type() == at::kInt && work.numel() == 2LL * a.B * a.nint + a.B + 1 + extra,
+              "jpeg: work int32 [2 * B * intervals + B + 1 (+ 1 with the block coder)]");
   a.qtab = tables.data_ptr<int>(); a.huff = a.qtab + 128;
   a.header = header.data_ptr<uint8_t>();
   a.coef = coef.data_ptr<int16_t>();
   a.base = reinterpret_cast<uint32_t*>(work.data_ptr<int>());     // [B + 1] first: what the host reads
-  a.lens = a.base + a.B + 1;
+  a.lens = a.base + a.B + 1 + extra;
   a.offs = a.lens + (long long)a.B * a.nint;
   return a;
+}
+
+// The block-parallel coder's buffers (jpeg.hip: block-parallel entropy coder).  blk int32
+// [B * mcus * blocks + B * intervals] = bits | ubits; scratch int32 [B * intervals * stride].
+JpegBlkArgs jpeg_blk_args(const JpegArgs& a, at::Tensor& work, at::Tensor& blk, at::Tensor& scratch, int64_t stride) {
+  CHECK_DEV(blk); CHECK_CONTIG(blk); CHECK_DEV(scratch); CHECK_CONTIG(scratch);
+  const long long mcus = (long long)a.mx * a.my, nblk = (long long)a.B * mcus * a.nb, nivals = (long long)a.B * a.nint;
+  const long long per = (a.restart < mcus ? (long long)a.restart : mcus) * a.nb;
+  // bit offsets within an interval are 32-bit words; the slot holds the worst case of every block
+  TORCH_CHECK((double)per * jpeg_blk_max_bits() < 4294967296.0, "jpeg: restart interval too long for 32-bit bit offsets");
+  TORCH_CHECK(stride == (per * jpeg_blk_max_bits() + 31) / 32 && stride < (1LL << 30),
+              "jpeg: stride = ceil(blocks per interval * max bits per block / 32)");
+  TORCH_CHECK(nblk < 256LL * 2147483647LL && nivals < 2147483647LL, "jpeg: batch too large for one launch");
+  TORCH_CHECK(blk.scalar_type() == at::kInt && blk.numel() == nblk + nivals, "jpeg: blk int32 [B * mcus * blocks + B * intervals]");
+  TORCH_CHECK(scratch.scalar_type() == at::kInt && scratch.numel() == nivals * stride,
+              "jpeg: scratch int32 [B * intervals * stride]");
+  JpegBlkArgs k;
+  k.bits = reinterpret_cast<uint32_t*>(blk.data_ptr<int>());
+  k.ubits = k.bits + nblk;
+  k.scratch = reinterpret_cast<uint32_t*>(scratch.data_ptr<int>());
+  k.stride = (uint32_t)stride;
+  k.err = reinterpret_cast<uint32_t*>(work.data_ptr<int>()) + a.B + 1;
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.coef) % 16 == 0, "jpeg: coef must be 16-byte aligned");
+  return k;
+}
+
+void jpeg_count_blocks(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
+                       at::Tensor& work, at::Tensor& blk, at::Tensor& scratch, int64_t stride, int64_t s420,
+                       int64_t restart) {
+  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, true);
+  launch_jpeg_count_blocks(a, jpeg_blk_args(a, work, blk, scratch, stride), cur_stream());
+}
+
+// out uint8 [total + 1]: the payload and, behind it, the write pass's error byte
+void jpeg_write_blocks(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
+                       at::Tensor& work, at::Tensor& blk, at::Tensor& scratch, int64_t stride, int64_t s420,
+                       int64_t restart, at::Tensor& out, int64_t total) {
+  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, true);
+  JpegBlkArgs k = jpeg_blk_args(a, work, blk, scratch, stride);
+  CHECK_DEV(out); CHECK_CONTIG(out);
+  TORCH_CHECK(out.scalar_type() == at::kByte && total > 0 && total < 2147483647LL && out.numel() == total + 1,
+              "jpeg: out uint8 [base[B] + 1]");
+  a.out = out.data_ptr<uint8_t>();
+  k.out_size = (uint32_t)total;
+  launch_jpeg_write_blocks(a, k, cur_stream());
 }
 
 void jpeg_count(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
@@ -1138,6 +1191,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("to_uint8", &to_uint8, nogil());
   m.def("jpeg_count", &jpeg_count, nogil());
   m.def("jpeg_write", &jpeg_write, nogil());
+  m.def("jpeg_count_blocks", &jpeg_count_blocks, nogil());
+  m.def("jpeg_write_blocks", &jpeg_write_blocks, nogil());
   m.def("jpeg_reconstruct", &jpeg_reconstruct, nogil());
   m.def("jpeg_entropy_decode", &jpeg_entropy_decode, nogil());
   m.def("jpeg_entropy_decode_chunked", &jpeg_entropy_decode_chunked, nogil());

@@ -173,10 +173,49 @@
 // separated by block-uniform barriers; validity and block scans, then the write pass) -> DC
 // prefix (one workgroup per interval) -> check (one thread per block).  The host cuts the groups
 // and stages them with the bytes.
+//
+// BLOCK-PARALLEL ENTROPY CODER (jpeg_format.entropy_blocks is its numpy model, jpeg_entropy_blk.h
+// the per-block coder and the stuffing piece): the bytes of the BYTE CONTRACT for any restart
+// interval, none included (no DRI: the image is one interval), with one lane per 8x8 block instead
+// of one per interval.  A block's code bits depend on its 64 coefficients and on the DC value of
+// the previous block of its component only, and both are in the coefficient buffer.
+//
+//   DC predictor.  Of block k of MCU m: Y blocks of an MCU follow each other (k > 0: block k - 1
+//   of the MCU), the first follows the last Y block of MCU m - 1; Cb / Cr follow Cb / Cr of MCU
+//   m - 1.  In the first MCU of an interval those are 0.
+//   Bits.  A lane runs the coder of the byte contract on its block without storing: its bit length
+//   (4 .. 1660; the bound is longest DC code + 11 + 63 * (longest AC code + 10)).
+//   Scan.  The exclusive scan of the lengths over the interval is every block's bit offset in the
+//   interval's unstuffed string; the sum is the string's bit count, ceil(bits / 8) its bytes.
+//   Pack.  A lane runs the same coder again and puts its bits, MSB first, at its offset into the
+//   string's 32-bit words; the lane of the interval's last block appends the 1-bits that pad the
+//   last byte.  A word that lies inside one block has one writer, which stores it.  Up to 7 blocks
+//   start in one word (a flat chroma block is 4 bits), so the first and the last word of a block
+//   are merged with atomicOr; exactly those words (the word every block starts in, and the word
+//   the interval ends in) were zeroed by the scan pass, one store per block, nothing else is.
+//   Stuff.  The string is cut into pieces of 32 bytes (the last one shorter); a lane counts its
+//   piece's 0xFF bytes, the scan of piece length + count over the interval is the piece's place
+//   in the interval's bytes, and the total + 2 (RSTn / EOI) is the interval's length, from which
+//   jpeg_scan_image_kernel and jpeg_scan_batch_kernel give the image offsets as before.  After
+//   the host has read those, the lanes count again, scan, and copy their pieces to their final
+//   place, a 0x00 behind every 0xFF; the interval's first lane writes the marker.
+//   Bounds.  The string of an interval has a slot of ceil(blocks * 1660 / 32) words.  Every word
+//   index is checked against the slot, every payload index against the payload's size; a refused
+//   index raises an error word (count passes: behind the image offsets, read with them) or byte
+//   (write pass: behind the payload, read with it) and stores nothing.
+//
+// Kernels: transform -> bits (one lane per block) -> scan (one workgroup per interval, tiles of
+// up to 1024 blocks with a running sum) -> pack (one lane per block) -> stuff<count> (one
+// workgroup per interval, tiles of up to 1024 pieces) -> the two scans of the interval coder ->
+// stuff<write> + header copy.  Every dependency is a kernel boundary or a barrier inside one
+// workgroup, every loop is bounded by a size known at launch.  Device memory beyond coefficients
+// and payload: one word per block, one per interval, and the slots (208 bytes per block, of which
+// 4 bytes per block + 4 per interval are zeroed).
 #include "common.h"
 #include "kernels.h"
 #include "jpeg_entropy_dec.h"
 #include "jpeg_entropy_sync.h"
+#include "jpeg_entropy_blk.h"
 
 namespace {
 
@@ -842,7 +881,179 @@ __global__ __launch_bounds__(256) void jpeg_block_check_kernel(JpegArgs a, JpegD
   if (!jpeg_sync_block_ok(a.coef + i * 64, q + (blk < a.nb - 2 ? 0 : 64))) atomicOr(y.words, 1u);
 }
 
+// ---------------------------------------------------------------------------------- block-parallel entropy coder
+constexpr int BLK_LANES = 256;
+
+// One lane per block (g = (image * mcus + MCU) * nb + block): its bit length.  Lanes diverge with
+// their blocks' contents (4 .. 1660 bits); the per-lane state is one coefficient chunk and a few
+// scalars.
+__global__ __launch_bounds__(BLK_LANES) void jpeg_blk_bits_kernel(JpegArgs a, JpegBlkArgs k) {
+  __shared__ uint32_t huff[HUFF_WORDS];
+  for (int i = threadIdx.x; i < HUFF_WORDS; i += BLK_LANES) huff[i] = (uint32_t)a.huff[i];
+  __syncthreads();
+  const long long per_img = (long long)a.mx * a.my * a.nb;
+  const long long g = (long long)blockIdx.x * BLK_LANES + threadIdx.x;
+  if (g >= (long long)a.B * per_img) return;
+  const long long r = g % per_img, m = r / a.nb;
+  const int blk = (int)(r % a.nb);
+  const int16_t* img = a.coef + (g - r) * 64;
+  const bool luma = blk < a.nb - 2;
+  JpegBlkSink<false> w;
+  jpeg_blk_code<false>(img + r * 64, jpeg_blk_pred(img, m, blk, a.nb, a.restart), huff + (luma ? 0 : 16),
+                       huff + 32 + (luma ? 0 : 256), w);
+  k.bits[g] = w.pos;
+}
+
+// One workgroup per interval (64 .. 1024 threads, tiles of blockDim blocks with a running sum):
+// bits[] becomes the exclusive scan of the lengths, ubits the interval's bit count.  Every word a
+// block starts in, and the one the interval ends in, is zeroed here: those are the only words the
+// pack pass merges into (all others have one writer, which stores).
+__global__ __launch_bounds__(1024) void jpeg_blk_scan_kernel(JpegArgs a, JpegBlkArgs k) {
+  __shared__ uint32_t sbuf[2 * 1024];
+  __shared__ uint32_t stot;
+  const int t = threadIdx.x, n = blockDim.x;
+  const long long gid = blockIdx.x;
+  const int b = (int)(gid / a.nint), it = (int)(gid % a.nint);
+  const int mcus = a.mx * a.my;
+  const long long m0 = (long long)it * a.restart;
+  const int nblk = (int)max(0LL, min((long long)a.restart, mcus - m0)) * a.nb;
+  uint32_t* bits = k.bits + ((long long)b * mcus + m0) * a.nb;
+  uint32_t* words = k.scratch + gid * k.stride;
+  uint32_t running = 0;
+  bool bad = false;
+  for (int i0 = 0; i0 < nblk; i0 += n) {
+    const int i = i0 + t;
+    const uint32_t v = i < nblk ? bits[i] : 0u;
+    const uint32_t inc = jpeg_block_scan<1024>(v, sbuf);
+    if (t == n - 1) stot = inc;
+    if (i < nblk) {
+      const uint32_t off = running + inc - v;
+      bits[i] = off;
+      if ((off >> 5) < k.stride) words[off >> 5] = 0u;
+      else bad = true;
+    }
+    __syncthreads();
+    running += stot;
+    __syncthreads();
+  }
+  if (t == 0) {
+    k.ubits[gid] = running;
+    if ((running >> 5) < k.stride) words[running >> 5] = 0u;
+    else if ((running >> 5) > k.stride || (running & 31u) != 0u) bad = true;
+  }
+  if (bad) atomicOr(k.err, 1u);
+}
+
+// One lane per block again: the same coder, storing at the block's bit offset.
+__global__ __launch_bounds__(BLK_LANES) void jpeg_blk_pack_kernel(JpegArgs a, JpegBlkArgs k) {
+  __shared__ uint32_t huff[HUFF_WORDS];
+  for (int i = threadIdx.x; i < HUFF_WORDS; i += BLK_LANES) huff[i] = (uint32_t)a.huff[i];
+  __syncthreads();
+  const int mcus = a.mx * a.my;
+  const long long per_img = (long long)mcus * a.nb;
+  const long long g = (long long)blockIdx.x * BLK_LANES + threadIdx.x;
+  if (g >= (long long)a.B * per_img) return;
+  const long long r = g % per_img, m = r / a.nb;
+  const int blk = (int)(r % a.nb);
+  const int16_t* img = a.coef + (g - r) * 64;
+  const bool luma = blk < a.nb - 2;
+  const long long it = m / a.restart, gid = (g / per_img) * a.nint + it;
+  const bool last = blk == a.nb - 1 && m == min((it + 1) * a.restart, (long long)mcus) - 1;
+  const uint32_t off = k.bits[g];
+  JpegBlkSink<true> w;
+  w.start(k.scratch + gid * k.stride, k.stride, off);
+  jpeg_blk_code<true>(img + r * 64, jpeg_blk_pred(img, m, blk, a.nb, a.restart), huff + (luma ? 0 : 16),
+                      huff + 32 + (luma ? 0 : 256), w);
+  w.finish(off, last);
+  if (w.bad) atomicOr(k.err, 1u);
+}
+
+// One workgroup per interval, one lane per piece of JPEG_BLK_PIECE unstuffed bytes (tiles of
+// blockDim pieces with a running sum): the stuffed length of every piece, its scan, and either the
+// interval's length with its marker (lens) or the bytes at their final place.
+template <bool WRITE>
+__global__ __launch_bounds__(1024) void jpeg_blk_stuff_kernel(JpegArgs a, JpegBlkArgs k) {
+  __shared__ uint32_t sbuf[2 * 1024];
+  __shared__ uint32_t stot;
+  const int t = threadIdx.x, n = blockDim.x;
+  const long long gid = blockIdx.x;
+  const int b = (int)(gid / a.nint), it = (int)(gid % a.nint);
+  const uint32_t* words = k.scratch + gid * k.stride;
+  const uint32_t ub = k.ubits[gid];
+  uint32_t ubytes = (ub >> 3) + ((ub & 7u) != 0u ? 1u : 0u);
+  bool bad = false;
+  if (ubytes > 4u * k.stride) {                      // stride < 2^30 (checked by the caller)
+    ubytes = 4u * k.stride;
+    bad = true;
+  }
+  const uint32_t npiece = (ubytes + JPEG_BLK_PIECE - 1u) / JPEG_BLK_PIECE;
+  const uint32_t dst = WRITE ? a.base[b] + (uint32_t)a.hdr_len + a.offs[gid] : 0u;
+  uint32_t running = 0;
+  for (uint32_t p0 = 0; p0 < npiece; p0 += (uint32_t)n) {
+    const uint32_t p = p0 + (uint32_t)t;
+    const uint32_t b0 = p * JPEG_BLK_PIECE, b1 = min(ubytes, b0 + JPEG_BLK_PIECE);
+    const uint32_t cnt = p < npiece ? jpeg_blk_stuff<false>(words, k.stride, b0, b1, nullptr, 0u, 0u, bad) : 0u;
+    const uint32_t inc = jpeg_block_scan<1024>(cnt, sbuf);
+    if (t == n - 1) stot = inc;
+    if (WRITE && p < npiece) jpeg_blk_stuff<true>(words, k.stride, b0, b1, a.out, dst + running + inc - cnt, k.out_size, bad);
+    __syncthreads();
+    running += stot;
+    __syncthreads();
+  }
+  if (t == 0) {
+    if (WRITE) {
+      const uint32_t at = dst + running;
+      if ((unsigned long long)at + 2ull <= (unsigned long long)k.out_size) {
+        a.out[at] = 0xff;
+        a.out[at + 1] = (uint8_t)(it + 1 < a.nint ? 0xD0u + (uint32_t)(it & 7) : 0xD9u);
+      } else {
+        bad = true;
+      }
+    } else {
+      a.lens[gid] = running + 2u;
+    }
+  }
+  if (bad) {
+    if (WRITE) a.out[k.out_size] = 1;                // the byte behind the payload
+    else atomicOr(k.err, 1u);
+  }
+}
+
 }  // namespace
+
+int jpeg_blk_max_bits() { return (int)JPEG_BLK_MAX_BITS; }
+
+static int blk_threads(long long items) {
+  const long long t = (items + 63) / 64 * 64;
+  return (int)(t < 64 ? 64 : (t > 1024 ? 1024 : t));
+}
+
+void launch_jpeg_count_blocks(const JpegArgs& a, const JpegBlkArgs& k, hipStream_t s) {
+  launch_zero(k.err, 4, s);
+  const long long mcus = (long long)a.B * a.mx * a.my;
+  const unsigned tg = (unsigned)((mcus + TR_WAVES - 1) / TR_WAVES);
+  if (a.nb == 6) hipLaunchKernelGGL(jpeg_transform_kernel<true>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
+  else hipLaunchKernelGGL(jpeg_transform_kernel<false>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
+  const unsigned bg = (unsigned)((mcus * a.nb + BLK_LANES - 1) / BLK_LANES);
+  const unsigned ig = (unsigned)((long long)a.B * a.nint);
+  const long long per = (long long)(a.restart < a.mx * a.my ? a.restart : a.mx * a.my) * a.nb;   // blocks per interval
+  hipLaunchKernelGGL(jpeg_blk_bits_kernel, dim3(bg), dim3(BLK_LANES), 0, s, a, k);
+  hipLaunchKernelGGL(jpeg_blk_scan_kernel, dim3(ig), dim3(blk_threads(per)), 0, s, a, k);
+  hipLaunchKernelGGL(jpeg_blk_pack_kernel, dim3(bg), dim3(BLK_LANES), 0, s, a, k);
+  // pieces per interval: sized for an eighth of the worst case, longer strings take more tiles
+  const int st = blk_threads(((long long)k.stride * 4 / JPEG_BLK_PIECE + 7) / 8);
+  hipLaunchKernelGGL(jpeg_blk_stuff_kernel<false>, dim3(ig), dim3(st), 0, s, a, k);
+  hipLaunchKernelGGL(jpeg_scan_image_kernel, dim3(a.B), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(jpeg_scan_batch_kernel, dim3(1), dim3(64), 0, s, a);
+}
+
+void launch_jpeg_write_blocks(const JpegArgs& a, const JpegBlkArgs& k, hipStream_t s) {
+  launch_zero(a.out + k.out_size, 1, s);
+  const unsigned ig = (unsigned)((long long)a.B * a.nint);
+  const int st = blk_threads(((long long)k.stride * 4 / JPEG_BLK_PIECE + 7) / 8);
+  hipLaunchKernelGGL(jpeg_blk_stuff_kernel<true>, dim3(ig), dim3(st), 0, s, a, k);
+  hipLaunchKernelGGL(jpeg_header_kernel, dim3(a.B), dim3(256), 0, s, a);
+}
 
 void launch_jpeg_count(const JpegArgs& a, hipStream_t s) {
   const long long mcus = (long long)a.B * a.mx * a.my;

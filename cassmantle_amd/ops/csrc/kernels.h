@@ -235,6 +235,23 @@ struct JpegArgs {
 void launch_jpeg_count(const JpegArgs& a, hipStream_t s);
 // entropy-coded data at the final offsets + headers: fills out[0 .. base[B])
 void launch_jpeg_write(const JpegArgs& a, hipStream_t s);
+// block-parallel entropy coder (block-parallel entropy coder section of jpeg.hip's header comment;
+// jpeg_entropy_blk.h).  With it a.restart = MCUs per interval (all of them without DRI), never 0.
+struct JpegBlkArgs {
+  uint32_t* bits = nullptr;          // [B][mx*my][nb] bit length of every block, then its bit offset in its interval
+  uint32_t* ubits = nullptr;         // [B][nint] bits of every interval's unstuffed string
+  uint32_t* scratch = nullptr;       // [B][nint][stride] the unstuffed strings, MSB first in 32-bit words
+  uint32_t stride = 0;               // words per interval = ceil(min(restart, mcus) * nb * JPEG_BLK_MAX_BITS / 32)
+  uint32_t* err = nullptr;           // one word, raised by a refused scratch index (behind base: read with it)
+  uint32_t out_size = 0;             // launch_jpeg_write_blocks: payload bytes = base[B]; out[out_size] is raised
+                                     // by a refused payload index
+};
+int jpeg_blk_max_bits();
+// transform + bits per block + scan per interval + pack + 0xFF count per piece + the scans of
+// launch_jpeg_count: fills coef, bits, ubits, scratch, err, lens, offs, base
+void launch_jpeg_count_blocks(const JpegArgs& a, const JpegBlkArgs& k, hipStream_t s);
+// the stuffed bytes at the final offsets + markers + headers: fills out[0 .. out_size], out[out_size] = error byte
+void launch_jpeg_write_blocks(const JpegArgs& a, const JpegBlkArgs& k, hipStream_t s);
 // inverse DCT of coef into planes, then upsampling + colour into dec (reads B, H, W, nb, mx, my,
 // qtab, coef only)
 void launch_jpeg_reconstruct(const JpegArgs& a, hipStream_t s);

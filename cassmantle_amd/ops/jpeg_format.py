@@ -286,6 +286,140 @@ def entropy(coef: np.ndarray, restart_mcus: int):
     return bytes(out), stats
 
 
+# ----------------------------------------------------------------------------- block-parallel entropy coder
+# The same bytes with the work divided per 8x8 block: the BLOCK-PARALLEL ENTROPY CODER section of
+# jpeg.hip's header comment; ops/csrc/jpeg_entropy_blk.h is the per-block coder and the stuffing
+# piece the kernels and the host program compile.
+BLK_STUFF_CHUNK = 32                   # unstuffed bytes per stuffing piece (jpeg_entropy_blk.h: JPEG_BLK_PIECE)
+
+
+@lru_cache(maxsize=None)
+def block_bits_bound() -> int:
+    """The most bits one block can code to, from the Huffman tables: the longest DC code + 11 value
+    bits, and 63 times the longest AC code + 10 value bits (no ZRL or EOB: every position is taken)."""
+    h = huff_table()
+    dc = max(int(v) >> 16 for v in np.concatenate([h[0:16], h[16:32]]))
+    ac = max(int(v) >> 16 for v in h[32:])
+    return dc + 11 + 63 * (ac + 10)
+
+
+def dc_predictors(coef: np.ndarray, restart_mcus: int) -> np.ndarray:
+    """int [mcus, nb]: the DC value every block's difference is taken against, from the geometry
+    alone: the previous block of the component in coding order (4:2:0: the Y blocks of an MCU
+    follow each other, the first follows the previous MCU's last; Cb / Cr follow the previous
+    MCU's), 0 for a component's first block of a restart interval."""
+    mcus, nb, _ = coef.shape
+    per = restart_mcus if restart_mcus else mcus
+    dc = coef[..., 0].astype(np.int64)
+    pred = np.zeros((mcus, nb), dtype=np.int64)
+    head = (np.arange(mcus) % per) == 0
+    prev = np.roll(dc, 1, axis=0)                       # the MCU before (row 0 is masked by head)
+    nl = nb - 2
+    pred[:, 0] = np.where(head, 0, prev[:, nl - 1])
+    pred[:, 1:nl] = dc[:, 0:nl - 1]
+    pred[:, nl:] = np.where(head[:, None], 0, prev[:, nl:])
+    return pred
+
+
+def _block_code(blk, pred: int, luma: bool, huff, stats: dict):
+    """One block's code bits as (value, bit count): the coder of :func:`entropy` on one block."""
+    dc_base, ac_base = (0, 32) if luma else (16, 32 + 256)
+    acc = n = 0
+    d = blk[0] - pred
+    cat = _category(d)
+    stats["max_dc_cat"] = max(stats["max_dc_cat"], cat)
+    h = int(huff[dc_base + cat])
+    acc, n = (acc << (h >> 16)) | (h & 0xFFFF), n + (h >> 16)
+    if cat:
+        acc, n = (acc << cat) | ((d if d >= 0 else d - 1) & ((1 << cat) - 1)), n + cat
+    run = 0
+    for k in range(1, 64):
+        v = blk[k]
+        if v == 0:
+            run += 1
+            continue
+        while run >= 16:
+            h = int(huff[ac_base + 0xF0])
+            acc, n = (acc << (h >> 16)) | (h & 0xFFFF), n + (h >> 16)
+            stats["zrl"] += 1
+            run -= 16
+        cat = _category(v)
+        h = int(huff[ac_base + (run << 4 | cat)])
+        acc, n = (acc << (h >> 16)) | (h & 0xFFFF), n + (h >> 16)
+        acc, n = (acc << cat) | ((v if v >= 0 else v - 1) & ((1 << cat) - 1)), n + cat
+        run = 0
+    if run:
+        h = int(huff[ac_base])
+        acc, n = (acc << (h >> 16)) | (h & 0xFFFF), n + (h >> 16)
+    return acc, n
+
+
+def entropy_blocks(coef: np.ndarray, restart_mcus: int, stuff_chunk: int = BLK_STUFF_CHUNK, stats: dict = None):
+    """What :func:`entropy` returns, computed the way the BLOCK-PARALLEL ENTROPY CODER says: per
+    restart interval the bit length of every block (DC difference against :func:`dc_predictors`),
+    the exclusive scan of the lengths, every block's bits packed at its offset into the unstuffed
+    string (the last byte padded with 1-bits), and the stuffing in pieces of ``stuff_chunk``
+    unstuffed bytes: 0xFF count per piece, scan, copy with the zeros inserted.
+
+    ``stats`` receives what tells where an input reaches: ``min_bits`` / ``max_bits`` (block bit
+    lengths), ``max_starts_per_word`` (blocks starting in one 32-bit word of an interval's string),
+    ``ff_two_blocks`` (unstuffed 0xFF bytes with a block boundary inside), ``ff_interval_end``
+    (intervals whose last unstuffed byte is 0xFF), ``ff_piece_end`` (0xFF bytes that are the last
+    byte of a full piece), ``ff_pairs`` (two consecutive unstuffed 0xFF bytes), ``unstuffed`` (bytes)."""
+    if int(stuff_chunk) != stuff_chunk or stuff_chunk < 1:
+        raise ValueError("jpeg: stuff_chunk must be a positive integer")
+    huff = huff_table()
+    mcus, nb, _ = coef.shape
+    per = restart_mcus if restart_mcus else mcus
+    nint = (mcus + per - 1) // per
+    out = bytearray()
+    st = {"stuffed": 0, "zrl": 0, "max_dc_cat": 0, "intervals": nint}
+    cov = {"min_bits": 1 << 30, "max_bits": 0, "max_starts_per_word": 0, "ff_two_blocks": 0, "ff_interval_end": 0,
+           "ff_piece_end": 0, "ff_pairs": 0, "unstuffed": 0}
+    pred = dc_predictors(coef, restart_mcus).tolist()
+    rows = coef.tolist()
+    for it in range(nint):
+        m0, m1 = it * per, min((it + 1) * per, mcus)
+        # 1. bits per block
+        codes = [_block_code(rows[m][b], pred[m][b], b < nb - 2, huff, st) for m in range(m0, m1) for b in range(nb)]
+        lens = np.asarray([n for _, n in codes], dtype=np.int64)
+        # 2. scan
+        offs = np.concatenate([[0], np.cumsum(lens)])
+        bits = int(offs[-1])
+        nbytes = (bits + 7) // 8
+        # 3. pack: every block ORs its bits into the zeroed string at its offset, then the padding
+        total = 0
+        for (val, n), o in zip(codes, offs[:-1].tolist()):
+            total |= val << (8 * nbytes - o - n)
+        total |= (1 << (8 * nbytes - bits)) - 1
+        u = np.frombuffer(total.to_bytes(nbytes, "big"), dtype=np.uint8)
+        # 4. stuff: count per piece, scan, copy
+        ff = u == 0xFF
+        npiece = (nbytes + stuff_chunk - 1) // stuff_chunk
+        cnt = np.add.reduceat(ff.astype(np.int64), np.arange(npiece) * stuff_chunk)
+        poff = np.arange(npiece) * stuff_chunk + np.concatenate([[0], np.cumsum(cnt)[:-1]])
+        body = bytearray(nbytes + int(cnt.sum()))
+        for p in range(npiece):
+            piece = u[p * stuff_chunk: (p + 1) * stuff_chunk].tobytes().replace(b"\xff", b"\xff\x00")
+            body[int(poff[p]): int(poff[p]) + len(piece)] = piece
+        st["stuffed"] += int(cnt.sum())
+        out += body
+        if it + 1 < nint:
+            out += bytes([0xFF, 0xD0 + (it & 7)])
+        cov["min_bits"] = min(cov["min_bits"], int(lens.min()))
+        cov["max_bits"] = max(cov["max_bits"], int(lens.max()))
+        cov["max_starts_per_word"] = max(cov["max_starts_per_word"], int(np.bincount(offs[:-1] >> 5).max()))
+        inner = offs[1:-1][(offs[1:-1] & 7) != 0] >> 3          # bytes with a block boundary inside
+        cov["ff_two_blocks"] += int(ff[np.unique(inner)].sum())
+        cov["ff_interval_end"] += int(ff[-1])
+        cov["ff_piece_end"] += int(ff[stuff_chunk - 1:: stuff_chunk].sum())
+        cov["ff_pairs"] += int((ff[:-1] & ff[1:]).sum())
+        cov["unstuffed"] += nbytes
+    if stats is not None:
+        stats.update(cov)
+    return bytes(out), st
+
+
 def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: int = 4,
                 return_stats: bool = False):
     """Baseline JPEG of uint8 ``[B, H, W, 3]`` (or ``[H, W, 3]``) images: one byte string per

@@ -86,6 +86,31 @@ def blur_kernel(cfg: Config) -> str:
     return k
 
 
+def jpeg_restart(cfg: Config, width: int):
+    """``(restart_mcus, entropy)`` for ops.jpeg_encode of an image ``width`` pixels wide, from
+    ``ModelConfig.jpeg_restart_mcus`` (0: one MCU row of the 4:2:0 encode, -1: no restart markers,
+    else that many MCUs) and ``ModelConfig.jpeg_entropy`` (interval | block).  An unknown coder is
+    an error, not the default, and so is -1 with the interval coder, which cannot write it."""
+    entropy = str(cfg.model.jpeg_entropy).lower()
+    if entropy not in ("interval", "block"):
+        raise ValueError(f"jpeg_entropy={cfg.model.jpeg_entropy!r}: expected interval or block")
+    r = int(cfg.model.jpeg_restart_mcus)
+    if r < -1:
+        raise ValueError(f"jpeg_restart_mcus={r}: expected -1 (no restart markers), 0 (one MCU row) or a count")
+    if r == -1:
+        if entropy != "block":
+            raise ValueError("jpeg_restart_mcus=-1 (no restart markers) needs jpeg_entropy=block")
+        return 0, entropy
+    return r or (int(width) + 15) // 16, entropy
+
+
+def _jpeg_encode_args(cfg: Config, width: int) -> dict:
+    """jpeg_restart as keyword arguments of ops.jpeg_encode; the default coder is not named, so
+    the default configuration makes the call it always made."""
+    restart, entropy = jpeg_restart(cfg, width)
+    return {"restart_mcus": restart} if entropy == "interval" else {"restart_mcus": restart, "entropy": entropy}
+
+
 def _device_pixels(img, dev: str) -> torch.Tensor:
     """The pixels of ``img`` on ``dev``: a DeviceImage is already in this GPU's HBM, anything else
     (an array, a PIL decode) is uploaded."""
@@ -137,12 +162,12 @@ def build_blur_jpeg_fn(cfg: Config, device: Optional[str] = None):
     if not (cfg.model.gpu_jpeg and cfg.model.gpu_blur) or not str(dev).startswith("cuda"):
         return None
     from .. import ops
+    jpeg_restart(cfg, 16)                   # a bad jpeg_entropy / jpeg_restart_mcus raises here, not per request
     if kernel == "pil":
         def blur_jpeg_exact(img, radii: Sequence[float], quality: int):
             x = _device_pixels(img, dev)
             buf = ops.gaussian_blur_pil(x, [float(r) for r in radii])      # ONE launch: [len(radii), H, W, 3]
-            restart = cfg.model.jpeg_restart_mcus or (x.shape[1] + 15) // 16      # 0: one MCU row
-            return ops.jpeg_encode(buf, quality=quality, restart_mcus=restart)
+            return ops.jpeg_encode(buf, quality=quality, **_jpeg_encode_args(cfg, x.shape[1]))
         return blur_jpeg_exact
 
     def blur_jpeg(img, radii: Sequence[float], quality: int):
@@ -155,8 +180,7 @@ def build_blur_jpeg_fn(cfg: Config, device: Optional[str] = None):
         buf = torch.empty((len(radii), *x.shape), device=x.device, dtype=torch.uint8)
         for i, r in enumerate(radii):
             ops.copy_(buf[i], ops.gaussian_blur(x, float(r)))
-        restart = cfg.model.jpeg_restart_mcus or (x.shape[1] + 15) // 16      # 0: one MCU row
-        return ops.jpeg_encode(buf, quality=quality, restart_mcus=restart)
+        return ops.jpeg_encode(buf, quality=quality, **_jpeg_encode_args(cfg, x.shape[1]))
     return blur_jpeg
 
 
@@ -174,11 +198,11 @@ def build_content_jpeg_fn(cfg: Config, device: Optional[str] = None):
         return None
     from .. import ops
     from ..game.content import DeviceImage
+    jpeg_restart(cfg, 16)                   # a bad jpeg_entropy / jpeg_restart_mcus raises here, not per request
 
     def content_jpeg(img, quality: int):
         x = img.tensor.to(dev, non_blocking=False)
-        restart = m.jpeg_restart_mcus or (x.shape[1] + 15) // 16      # 0: one MCU row
-        outs, decoded = ops.jpeg_encode(x, quality=quality, restart_mcus=restart, return_decoded=True)
+        outs, decoded = ops.jpeg_encode(x, quality=quality, return_decoded=True, **_jpeg_encode_args(cfg, x.shape[1]))
         return outs[0], DeviceImage(decoded[0])
     return content_jpeg
 

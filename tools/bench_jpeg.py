@@ -49,6 +49,18 @@ alone; and one more image, the worst case of that path: 512 x 512 noise (``tests
 PIL-encoded at quality 75 without restart markers.
 
     python tools/bench_jpeg.py --decode [--res 512 1024] [--reps 2] [--out profiles/jpeg_decode.jsonl]
+
+``--entropy block`` compares the two entropy coders of ``ops.jpeg_encode`` in the prewarm (default)
+or the ``--content`` mode: per ``--jpeg_restart_mcus`` setting (0: one MCU row, N: N MCUs, -1: no
+restart markers) the block-parallel coder (``jpeg_entropy=block``) against the interval coder at the
+same setting (for -1, which the interval coder cannot write, against its one-MCU-row default), with
+``blur_kernel=pil``, all rows interleaved ``--reps`` times after a warm-up of each; ``--content``
+adds the parent's ``.cpu()`` + PIL encode.  Per record: host wall time, CPU time, JPEG bytes, the
+block coder's device memory (allocated / zeroed per call), and the device time (HIP events,
+nothing else queued) of the encode's two launch groups on the same pixels: count phase (transform,
+the same kernel for both coders, + everything up to the image offsets) and write phase.
+
+    python tools/bench_jpeg.py --entropy block [--content] [--jpeg_restart_mcus 0 4 -1] [--out profiles/jpeg_block.jsonl]
 """
 import argparse
 import io
@@ -114,6 +126,148 @@ def encode_device_ms(batch, restart: int, iters: int = 5):
         torch.cuda.synchronize()
         best = [min(best[0], ev[0].elapsed_time(ev[1])), min(best[1], t0.elapsed_time(ev[2]))]
     return best
+
+
+def block_buffers(B: int, H: int, W: int, restart: int):
+    """(nint, stride, bytes allocated, bytes zeroed per call) of the block coder's device memory
+    beyond coefficients and payload; ``restart`` 0 = no restart markers."""
+    from cassmantle_amd.ops import jpeg_format as jf
+    _, nb, mx, my = jf.geometry(H, W, "420")
+    per = min(restart, mx * my) if restart else mx * my
+    nint = -(-mx * my // per)
+    stride = (per * nb * jf.block_bits_bound() + 31) // 32
+    nblk = B * mx * my * nb
+    return nint, stride, 4 * (B * nint * stride + nblk + B * nint + 1), 4 * (nblk + B * nint) + 4 + 1
+
+
+def encode_blocks_device_ms(batch, restart: int, iters: int = 5):
+    """encode_device_ms for ``entropy="block"`` (``restart`` 0 = no restart markers): (transform +
+    bits + scan + pack + piece counts + scans, stuffed write + headers) in ms."""
+    import torch
+    from cassmantle_amd import ops
+    from cassmantle_amd.ops import jpeg_format as jf
+    from cassmantle_amd.ops._ext import ext
+    B, H, W, _ = batch.shape
+    _, nb, mx, my = jf.geometry(H, W, "420")
+    nint, stride, _, _ = block_buffers(B, H, W, restart)
+    tables, header = ops._jpeg_plan(batch.device, H, W, QUALITY, "420", restart)
+    coef = torch.empty((B, mx * my, nb, 64), device="cuda", dtype=torch.int16)
+    work = torch.empty(2 * B * nint + B + 2, device="cuda", dtype=torch.int32)
+    blk = torch.empty(B * mx * my * nb + B * nint, device="cuda", dtype=torch.int32)
+    scratch = torch.empty(B * nint * stride, device="cuda", dtype=torch.int32)
+    best = [1e9, 1e9]
+    for _ in range(iters):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        torch.cuda.synchronize()
+        ev[0].record()
+        ext().jpeg_count_blocks(batch, tables, header, coef, work, blk, scratch, stride, 1, restart)
+        ev[1].record()
+        total = int(work[B].item())
+        out = torch.empty(total + 1, device="cuda", dtype=torch.uint8)
+        torch.cuda.synchronize()
+        ev[2].record()
+        ext().jpeg_write_blocks(batch, tables, header, coef, work, blk, scratch, stride, 1, restart, out, total)
+        ev[3].record()
+        torch.cuda.synchronize()
+        best = [min(best[0], ev[0].elapsed_time(ev[1])), min(best[1], ev[2].elapsed_time(ev[3]))]
+    return best
+
+
+def block_main(a, emit) -> int:
+    """--entropy block: the block-parallel coder against the interval coder (see the module text)."""
+    import numpy as np
+    import torch
+    from cassmantle_amd import ops
+    from cassmantle_amd.config import Config
+    from cassmantle_amd.game.content import DeviceImage
+    from cassmantle_amd.game.imaging import encode_jpeg
+    from cassmantle_amd.runtime.factory import build_blur_fn, build_blur_jpeg_fn, build_content_jpeg_fn, jpeg_restart
+
+    def config(entropy, setting):
+        c = Config()
+        c.model.gpu_jpeg = c.model.gpu_jpeg_content = True
+        c.model.blur_kernel = "pil"
+        c.model.jpeg_entropy, c.model.jpeg_restart_mcus = entropy, setting
+        return c
+
+    for res in a.res:
+        img = source_image(res).copy()
+        jpeg = encode_jpeg(img, QUALITY)
+        dimg = DeviceImage(torch.from_numpy(img).cuda())
+        dimg.host()
+        blur_fn = build_blur_fn(config("interval", 0), "cuda")
+        radii = [i * BUCKET for i in range(1, int(MAX_BLUR / BUCKET) + 1)]
+        # rows: (entropy, setting, the yardstick's setting); the interval coder has no -1
+        rows = []
+        for setting in a.jpeg_restart_mcus:
+            yard = ("interval", setting if setting >= 0 else 0)
+            if yard not in rows:
+                rows.append(yard)
+            rows.append(("block", setting))
+        pixels = dimg.tensor[None].contiguous() if a.content else ops.gaussian_blur_pil(dimg.tensor, radii)
+
+        def run(entropy, setting, tag):
+            cfg = config(entropy, setting)
+            restart, _ = jpeg_restart(cfg, res)
+            rec = {"res": res, "mode": "content" if a.content else "prewarm", "entropy": entropy,
+                   "jpeg_restart_mcus": setting, "restart_mcus": restart}
+            if a.content:
+                fn = build_content_jpeg_fn(cfg, "cuda")
+                d = DeviceImage(dimg.tensor)
+                torch.cuda.synchronize()
+                w0, c0 = time.perf_counter(), time.process_time()
+                data, _ = fn(d, QUALITY)
+                torch.cuda.synchronize()
+                wall, cpu = time.perf_counter() - w0, time.process_time() - c0
+                size, outs = len(data), [data]
+            else:
+                n, wall, cpu, got = prewarm_once(blur_fn, build_blur_jpeg_fn(cfg, "cuda"), dimg, jpeg, tag)
+                outs = [v for r, v in sorted(got.items()) if r > 0]
+                size = sum(len(v) for v in outs)
+                rec["buckets"] = n
+            rec.update(wall_ms=round(wall * 1e3, 3), cpu_ms=round(cpu * 1e3, 3), jpeg_bytes=size)
+            return rec, outs
+
+        def run_parent():
+            d = DeviceImage(dimg.tensor)                # fresh: no cached host copy
+            torch.cuda.synchronize()
+            w0, c0 = time.perf_counter(), time.process_time()
+            data = encode_jpeg(d, QUALITY)
+            wall, cpu = time.perf_counter() - w0, time.process_time() - c0
+            return {"res": res, "mode": "content", "entropy": "parent (.cpu() + PIL)", "wall_ms": round(wall * 1e3, 3),
+                    "cpu_ms": round(cpu * 1e3, 3), "jpeg_bytes": len(data)}
+
+        equal = {}
+        for entropy, setting in rows:                   # warm-up, and the bytes once
+            _, outs = run(entropy, setting, f"warm-{entropy}-{setting}")
+            restart, _ = jpeg_restart(config(entropy, setting), res)
+            if entropy == "block":
+                cpu_pixels = pixels[:1].cpu().numpy()        # the numpy reference takes seconds per image
+                equal[setting] = outs[:1] == ops.reference.jpeg_encode(cpu_pixels, QUALITY, "420", restart)
+        if a.content:
+            run_parent()
+        for rep in range(a.reps):
+            if a.content:
+                emit(dict(run_parent(), rep=rep))
+            for entropy, setting in rows:
+                rec, _ = run(entropy, setting, f"{entropy}-{setting}-{rep}")
+                if entropy == "block":
+                    rec["first_image_equals_reference"] = bool(equal[setting])
+                emit(dict(rec, rep=rep))
+        for entropy, setting in rows:                   # device time of the two launch groups
+            restart, _ = jpeg_restart(config(entropy, setting), res)
+            rec = {"res": res, "mode": "content" if a.content else "prewarm", "entropy": entropy,
+                   "jpeg_restart_mcus": setting, "restart_mcus": restart, "images": int(pixels.shape[0])}
+            if entropy == "block":
+                cnt, wr = encode_blocks_device_ms(pixels, restart)
+                _, _, alloc, zeroed = block_buffers(pixels.shape[0], res, res, restart)
+                rec.update(scratch_bytes_allocated=alloc, scratch_bytes_zeroed=zeroed)
+            else:
+                cnt, wr = encode_device_ms(pixels, restart)
+                nint = -(-((res + 15) // 16) ** 2 // restart)
+                rec.update(scratch_bytes_allocated=8 * pixels.shape[0] * nint, scratch_bytes_zeroed=0)
+            emit(dict(rec, count_phase_device_ms=round(cnt, 4), write_phase_device_ms=round(wr, 4)))
+    return 0
 
 
 def reconstruct_device_ms(t, restart: int, iters: int = 5) -> float:
@@ -414,6 +568,10 @@ def main(argv=None) -> int:
     ap.add_argument("--content", action="store_true", help="the content JPEG of one new image (see above)")
     ap.add_argument("--blur-kernel", choices=["pil"], default=None,
                     help="the prewarm comparison with blur_kernel=pil as a third row (see above)")
+    ap.add_argument("--entropy", choices=["block"], default=None,
+                    help="the block-parallel entropy coder against the interval coder, prewarm or --content (see above)")
+    ap.add_argument("--jpeg_restart_mcus", type=int, nargs="+", default=[0, 4, -1],
+                    help="--entropy block: the settings compared (0: one MCU row, -1: no restart markers)")
     a = ap.parse_args(argv)
     import numpy as np
     import torch
@@ -436,6 +594,11 @@ def main(argv=None) -> int:
             sink.write(line + "\n")
             sink.flush()
 
+    if a.entropy:
+        rc = block_main(a, emit)
+        if sink:
+            sink.close()
+        return rc
     if a.decode or a.content or a.blur_kernel:
         rc = decode_main(a, emit) if a.decode else (content_main(a, emit) if a.content else blur_kernel_main(a, emit))
         if sink:
