@@ -134,6 +134,10 @@ class ModelConfig:
     # lane per 8x8 block whatever the interval, the same bytes; profiles/jpeg_block.jsonl).
     # interval: today's path
     jpeg_entropy: str = "interval"
+    # the Huffman tables of ops.jpeg_encode: standard (Annex K, today's bytes) | optimized (every
+    # image's own tables, built on the device: what PIL's optimize=True writes; the same pixels in
+    # fewer bytes, profiles/jpeg_huffman.jsonl)
+    jpeg_huffman: str = "standard"
     # the content JPEG itself (radius 0, the bytes the content version hashes) encoded on the GPU
     # too, and its DECODED pixels (computed there from the same coefficients) registered as the
     # blur source: the image never crosses to the host, and masked bytes no longer depend on

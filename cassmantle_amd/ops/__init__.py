@@ -844,10 +844,28 @@ def _jpeg_plan(device, H: int, W: int, quality: int, sampling: str, restart_mcus
 
 
 JPEG_ENTROPY_CODERS = ("interval", "block")
+JPEG_HUFFMAN_MODES = ("standard", "optimized")
+_JPEG_OPT_PLANS: dict = {}     # (device, H, W, quality, sampling, restart_mcus) -> (tables, header parts, split) on the device
+
+
+def _jpeg_opt_plan(device, H: int, W: int, quality: int, sampling: str, restart_mcus: int):
+    """The constant inputs of an encode with optimised Huffman tables: the tables of
+    :func:`_jpeg_plan` (their Huffman words are not read), the header bytes before the DHT segment
+    followed by those behind it, and the length of the first part."""
+    from . import jpeg_format as jf
+    key = (device, H, W, quality, sampling, restart_mcus)
+    plan = _JPEG_OPT_PLANS.get(key)
+    if plan is None:
+        pre, suf = jf.header_parts(H, W, quality, sampling, restart_mcus)
+        if len(_JPEG_OPT_PLANS) >= 64:
+            _JPEG_OPT_PLANS.clear()
+        plan = _JPEG_OPT_PLANS[key] = (_jpeg_plan(device, H, W, quality, sampling, restart_mcus)[0],
+                                       torch.frombuffer(bytearray(pre + suf), dtype=torch.uint8).to(device), len(pre))
+    return plan
 
 
 def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: int = 4,
-                return_decoded: bool = False, entropy: str = "interval"):
+                return_decoded: bool = False, entropy: str = "interval", huffman: str = "standard"):
     """Baseline JPEG (JFIF) of uint8 ``[B, H, W, 3]`` / ``[H, W, 3]`` images (a tensor, or a
     ``DeviceImage``): one complete JPEG byte string per image, bit for bit what
     ``ops.reference.jpeg_encode`` writes (the contract: ops/csrc/jpeg.hip).  ``sampling`` "420" |
@@ -857,6 +875,13 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
     block whatever the restart interval, the same bytes; it accepts ``restart_mcus >= 0``, so it
     writes a stream without restart markers (what PIL writes, and the smallest) on the device.
     Any other value is a ``ValueError``; off the HIP path the argument selects nothing.
+
+    ``huffman="optimized"``: every image is coded with, and carries in its DHT, the Huffman tables
+    libjpeg's ``optimize`` builds for the image's own coefficients (the optimised Huffman tables
+    section of ops/csrc/jpeg.hip): smaller streams, the same pixels.  The symbol histogram and the
+    tables are built on the device between the transform and the coder's count pass; the host
+    flow below does not change (every image's header length rides with the image offsets).  Any
+    value but ``"standard"`` / ``"optimized"`` is a ``ValueError``.
 
     ``return_decoded``: ``(bytes per image, decoded)`` instead, ``decoded`` the uint8
     ``[B, H, W, 3]`` pixels a libjpeg decoder (PIL) gives for those bytes, bit for bit
@@ -871,16 +896,18 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
     the payload."""
     if entropy not in JPEG_ENTROPY_CODERS:
         raise ValueError(f"jpeg_encode: entropy must be one of {JPEG_ENTROPY_CODERS}, not {entropy!r}")
+    if huffman not in JPEG_HUFFMAN_MODES:
+        raise ValueError(f"jpeg_encode: huffman must be one of {JPEG_HUFFMAN_MODES}, not {huffman!r}")
     t = getattr(images, "tensor", images)
     if not isinstance(t, torch.Tensor):
-        outs = ref.jpeg_encode(images, quality, sampling, restart_mcus)
+        outs = ref.jpeg_encode(images, quality, sampling, restart_mcus, huffman=huffman)
         return (outs, ref.jpeg_decoded(images, quality, sampling)) if return_decoded else outs
     if t.dim() == 3:
         t = t[None]
     if t.dim() != 4 or t.shape[-1] != 3 or t.dtype != torch.uint8 or t.numel() == 0:
         raise ValueError("jpeg_encode: uint8 [B, H, W, 3] or [H, W, 3] expected")
     if not _use_hip(t):
-        outs = ref.jpeg_encode(t, quality, sampling, restart_mcus)
+        outs = ref.jpeg_encode(t, quality, sampling, restart_mcus, huffman=huffman)
         if not return_decoded:
             return outs
         return outs, torch.from_numpy(ref.jpeg_decoded(t, quality, sampling)).to(t.device)
@@ -892,7 +919,19 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
         raise ValueError("jpeg_encode: restart_mcus >= 0")
     B, H, W, _ = t.shape
     _, nb, mx, my = jf.geometry(H, W, sampling)
-    tables, header = _jpeg_plan(t.device, H, W, quality, sampling, restart_mcus)
+    optimized = huffman == "optimized"
+    opt, nopt, sfx = (), 0, ""
+    if optimized:
+        # the image's tables and header are built on the device: counts | code words, headers
+        jf.check_count_range(mx * my * nb)
+        if B > 65535:
+            raise ValueError("jpeg_encode: at most 65535 images per call with optimised Huffman tables")
+        tables, header, split = _jpeg_opt_plan(t.device, H, W, quality, sampling, restart_mcus)
+        hopt = torch.empty(2 * B * 544, device=t.device, dtype=torch.int32)
+        hdrs = torch.empty(B * (header.numel() + 4 + 4 * (17 + 256)), device=t.device, dtype=torch.uint8)
+        opt, nopt, sfx = (hopt, hdrs, split), B, "_opt"
+    else:
+        tables, header = _jpeg_plan(t.device, H, W, quality, sampling, restart_mcus)
     t = t.contiguous()
     per = min(restart_mcus, mx * my) if restart_mcus else mx * my          # MCUs per interval
     nint = (mx * my + per - 1) // per
@@ -901,26 +940,37 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
     if entropy == "block":
         # an interval's unstuffed string has a slot for the worst case of every block; only the
         # words blocks start in are zeroed (by the scan pass), nothing here
-        stride = (per * nb * jf.block_bits_bound() + 31) // 32
-        work = torch.empty(2 * B * nint + B + 2, device=t.device, dtype=torch.int32)
+        bound = jf.block_bits_bound_optimized() if optimized else jf.block_bits_bound()
+        stride = (per * nb * bound + 31) // 32
+        work = torch.empty(2 * B * nint + B + 2 + nopt, device=t.device, dtype=torch.int32)
         blk = torch.empty(B * mx * my * nb + B * nint, device=t.device, dtype=torch.int32)
         scratch = torch.empty(B * nint * stride, device=t.device, dtype=torch.int32)
-        ext().jpeg_count_blocks(t, tables, header, coef, work, blk, scratch, stride, s420, restart_mcus)
-        base = work[: B + 2].cpu().tolist()           # device-to-host copy 1: the image offsets + the error word
+        getattr(ext(), "jpeg_count_blocks" + sfx)(t, tables, header, coef, work, blk, scratch, stride, s420,
+                                                  restart_mcus, *opt)
+        # device-to-host copy 1: the image offsets + the error word (+ the header lengths)
+        base = work[: B + 2 + nopt].cpu().tolist()
+        hdr_lens, base = base[B + 2:], base[: B + 2]
         if base.pop():
             raise RuntimeError("jpeg_encode: the block coder refused a scratch index (a block over the bits bound)")
+        if not all(hdr_lens):
+            raise ValueError("jpeg: a Huffman code longer than 32 bits")
         out = torch.empty(base[-1] + 1, device=t.device, dtype=torch.uint8)
-        ext().jpeg_write_blocks(t, tables, header, coef, work, blk, scratch, stride, s420, restart_mcus, out, base[-1])
+        getattr(ext(), "jpeg_write_blocks" + sfx)(t, tables, header, coef, work, blk, scratch, stride, s420,
+                                                  restart_mcus, out, base[-1], *opt)
         host = out.cpu().numpy()                      # device-to-host copy 2: the payload + the error byte
         if host[-1]:
             raise RuntimeError("jpeg_encode: the block coder refused a payload index")
         mv = memoryview(host)
     else:
-        work = torch.empty(2 * B * nint + B + 1, device=t.device, dtype=torch.int32)
-        ext().jpeg_count(t, tables, header, coef, work, s420, restart_mcus)
-        base = work[: B + 1].cpu().tolist()               # device-to-host copy 1: the image offsets
+        work = torch.empty(2 * B * nint + B + 1 + nopt, device=t.device, dtype=torch.int32)
+        getattr(ext(), "jpeg_count" + sfx)(t, tables, header, coef, work, s420, restart_mcus, *opt)
+        # device-to-host copy 1: the image offsets (+ the header lengths)
+        base = work[: B + 1 + nopt].cpu().tolist()
+        hdr_lens, base = base[B + 1:], base[: B + 1]
+        if not all(hdr_lens):
+            raise ValueError("jpeg: a Huffman code longer than 32 bits")
         out = torch.empty(base[-1], device=t.device, dtype=torch.uint8)
-        ext().jpeg_write(t, tables, header, coef, work, s420, restart_mcus, out, base[-1])
+        getattr(ext(), "jpeg_write" + sfx)(t, tables, header, coef, work, s420, restart_mcus, out, base[-1], *opt)
         mv = memoryview(out.cpu().numpy())                # device-to-host copy 2: the payload
     outs = [bytes(mv[base[i]: base[i + 1]]) for i in range(B)]
     if not return_decoded:

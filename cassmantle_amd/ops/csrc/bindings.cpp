@@ -863,8 +863,19 @@ void decode_attention(const at::Tensor& q, const at::Tensor& k_cache, const at::
 // after phase 1's offsets reach the host).  tables: int32 [128 + 544] = quantisation | Huffman.
 // blocks: the block-parallel coder's call: restart 0 = no restart markers (one interval), and work has
 // one more word behind base (the error word)
+// opt: the buffers of the optimised Huffman tables (jpeg.hip: optimised Huffman tables): hopt int32
+// [2 * B * 544] = symbol counts | every image's code words, hdrs uint8 [B * cap] every image's
+// header, cap = header bytes + 4 + 4 * (17 + 256); header = the bytes before the DHT segment
+// (split of them) followed by those behind it; work has B more words behind base (and the error
+// word): every image's header length
+struct JpegOptBufs {
+  at::Tensor hopt, hdrs;
+  int64_t split = 0;
+};
+
 JpegArgs jpeg_args(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                   at::Tensor& work, int64_t s420, int64_t restart, bool blocks = false) {
+                   at::Tensor& work, int64_t s420, int64_t restart, bool blocks = false,
+                   const JpegOptBufs* opt = nullptr) {
   CHECK_DEV(images); CHECK_CONTIG(images); CHECK_DEV(tables); CHECK_CONTIG(tables); CHECK_DEV(header);
   CHECK_CONTIG(header); CHECK_DEV(coef); CHECK_CONTIG(coef); CHECK_DEV(work); CHECK_CONTIG(work);
   TORCH_CHECK(images.scalar_type() == at::kByte && images.dim() == 4 && images.size(3) == 3 && images.numel() > 0,
@@ -888,33 +899,50 @@ JpegArgs jpeg_args(const at::Tensor& images, const at::Tensor& tables, const at:
   a.restart = (int)restart;
   a.nint = (int)((mcus + restart - 1) / restart);
   a.hdr_len = (int)header.numel();
-  // 32-bit payload offsets: bound by the coder's worst case (20 + 63 * 26 bits per block, every
-  // byte stuffed, one padding byte and one marker per interval)
-  TORCH_CHECK((double)a.B * ((double)a.hdr_len + (double)mcus * a.nb * 416 + (double)a.nint * 3) < 2147483648.0,
+  const int hdr_cap = a.hdr_len + (opt ? 4 + 4 * (17 + 256) : 0);
+  // 32-bit payload offsets: bound by the coder's worst case (20 + 63 * 26 bits per block, 27 + 63 * 26
+  // with optimised tables, every byte stuffed, one padding byte and one marker per interval)
+  TORCH_CHECK((double)a.B * ((double)hdr_cap + (double)mcus * a.nb * (opt ? 417 : 416) + (double)a.nint * 3) < 2147483648.0,
               "jpeg: batch too large for 32-bit payload offsets");
   TORCH_CHECK(coef.scalar_type() == at::kShort && coef.numel() == (long long)a.B * mcus * a.nb * 64,
               "jpeg: coef int16 [B, mcus, blocks, 64]");
-  const int extra = blocks ? 1 : 0;
+  const int extra = (blocks ? 1 : 0) + (opt ? a.B : 0);
   TORCH_CHECK(work.scalar_type() == at::kInt && work.numel() == 2LL * a.B * a.nint + a.B + 1 + extra,
-              "jpeg: work int32 [2 * B * intervals + B + 1 (+ 1 with the block coder)]");
+              "jpeg: work int32 [2 * B * intervals + B + 1 (+ 1 with the block coder) (+ B with optimised tables)]");
   a.qtab = tables.data_ptr<int>(); a.huff = a.qtab + 128;
   a.header = header.data_ptr<uint8_t>();
   a.coef = coef.data_ptr<int16_t>();
   a.base = reinterpret_cast<uint32_t*>(work.data_ptr<int>());     // [B + 1] first: what the host reads
   a.lens = a.base + a.B + 1 + extra;
   a.offs = a.lens + (long long)a.B * a.nint;
+  if (opt) {
+    CHECK_DEV(opt->hopt); CHECK_CONTIG(opt->hopt); CHECK_DEV(opt->hdrs); CHECK_CONTIG(opt->hdrs);
+    TORCH_CHECK(a.B <= 65535, "jpeg: at most 65535 images per call with optimised Huffman tables");
+    TORCH_CHECK(mcus * a.nb * 64 < 2147483648LL, "jpeg: optimised Huffman tables count symbols in 32-bit words");
+    TORCH_CHECK(opt->split > 0 && opt->split < a.hdr_len, "jpeg: header = bytes before the DHT segment | bytes behind it");
+    TORCH_CHECK(opt->hopt.scalar_type() == at::kInt && opt->hopt.numel() == 2LL * a.B * 544, "jpeg: hopt int32 [2 * B * 544]");
+    TORCH_CHECK(opt->hdrs.scalar_type() == at::kByte && opt->hdrs.numel() == (long long)a.B * hdr_cap,
+                "jpeg: hdrs uint8 [B * (header bytes + 4 + 4 * (17 + 256))]");
+    a.freq = reinterpret_cast<uint32_t*>(opt->hopt.data_ptr<int>());
+    a.ihuff = a.freq + (long long)a.B * 544;
+    a.hdrs = opt->hdrs.data_ptr<uint8_t>();
+    a.hdr_cap = hdr_cap;
+    a.hdr_split = (int)opt->split;
+    a.hdr_lens = a.base + a.B + 1 + (blocks ? 1 : 0);
+  }
   return a;
 }
 
 // The block-parallel coder's buffers (jpeg.hip: block-parallel entropy coder).  blk int32
 // [B * mcus * blocks + B * intervals] = bits | ubits; scratch int32 [B * intervals * stride].
 JpegBlkArgs jpeg_blk_args(const JpegArgs& a, at::Tensor& work, at::Tensor& blk, at::Tensor& scratch, int64_t stride) {
+  const int max_bits = a.ihuff != nullptr ? jpeg_blk_max_bits_optimized() : jpeg_blk_max_bits();
   CHECK_DEV(blk); CHECK_CONTIG(blk); CHECK_DEV(scratch); CHECK_CONTIG(scratch);
   const long long mcus = (long long)a.mx * a.my, nblk = (long long)a.B * mcus * a.nb, nivals = (long long)a.B * a.nint;
   const long long per = (a.restart < mcus ? (long long)a.restart : mcus) * a.nb;
   // bit offsets within an interval are 32-bit words; the slot holds the worst case of every block
-  TORCH_CHECK((double)per * jpeg_blk_max_bits() < 4294967296.0, "jpeg: restart interval too long for 32-bit bit offsets");
-  TORCH_CHECK(stride == (per * jpeg_blk_max_bits() + 31) / 32 && stride < (1LL << 30),
+  TORCH_CHECK((double)per * max_bits < 4294967296.0, "jpeg: restart interval too long for 32-bit bit offsets");
+  TORCH_CHECK(stride == (per * max_bits + 31) / 32 && stride < (1LL << 30),
               "jpeg: stride = ceil(blocks per interval * max bits per block / 32)");
   TORCH_CHECK(nblk < 256LL * 2147483647LL && nivals < 2147483647LL, "jpeg: batch too large for one launch");
   TORCH_CHECK(blk.scalar_type() == at::kInt && blk.numel() == nblk + nivals, "jpeg: blk int32 [B * mcus * blocks + B * intervals]");
@@ -961,6 +989,47 @@ void jpeg_write(const at::Tensor& images, const at::Tensor& tables, const at::Te
   JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart);
   CHECK_DEV(out); CHECK_CONTIG(out);
   // total = base[B] as read back by the caller: every store of the write pass lands below it
+  TORCH_CHECK(out.scalar_type() == at::kByte && total > 0 && out.numel() == total, "jpeg: out uint8 [base[B]]");
+  a.out = out.data_ptr<uint8_t>();
+  launch_jpeg_write(a, cur_stream());
+}
+
+// The same four calls with optimised Huffman tables (JpegOptBufs above).
+void jpeg_count_blocks_opt(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
+                           at::Tensor& work, at::Tensor& blk, at::Tensor& scratch, int64_t stride, int64_t s420,
+                           int64_t restart, at::Tensor& hopt, at::Tensor& hdrs, int64_t split) {
+  const JpegOptBufs opt{hopt, hdrs, split};
+  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, true, &opt);
+  launch_jpeg_count_blocks(a, jpeg_blk_args(a, work, blk, scratch, stride), cur_stream());
+}
+
+void jpeg_write_blocks_opt(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
+                           at::Tensor& work, at::Tensor& blk, at::Tensor& scratch, int64_t stride, int64_t s420,
+                           int64_t restart, at::Tensor& out, int64_t total, at::Tensor& hopt, at::Tensor& hdrs,
+                           int64_t split) {
+  const JpegOptBufs opt{hopt, hdrs, split};
+  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, true, &opt);
+  JpegBlkArgs k = jpeg_blk_args(a, work, blk, scratch, stride);
+  CHECK_DEV(out); CHECK_CONTIG(out);
+  TORCH_CHECK(out.scalar_type() == at::kByte && total > 0 && total < 2147483647LL && out.numel() == total + 1,
+              "jpeg: out uint8 [base[B] + 1]");
+  a.out = out.data_ptr<uint8_t>();
+  k.out_size = (uint32_t)total;
+  launch_jpeg_write_blocks(a, k, cur_stream());
+}
+
+void jpeg_count_opt(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
+                    at::Tensor& work, int64_t s420, int64_t restart, at::Tensor& hopt, at::Tensor& hdrs, int64_t split) {
+  const JpegOptBufs opt{hopt, hdrs, split};
+  launch_jpeg_count(jpeg_args(images, tables, header, coef, work, s420, restart, false, &opt), cur_stream());
+}
+
+void jpeg_write_opt(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
+                    at::Tensor& work, int64_t s420, int64_t restart, at::Tensor& out, int64_t total, at::Tensor& hopt,
+                    at::Tensor& hdrs, int64_t split) {
+  const JpegOptBufs opt{hopt, hdrs, split};
+  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, false, &opt);
+  CHECK_DEV(out); CHECK_CONTIG(out);
   TORCH_CHECK(out.scalar_type() == at::kByte && total > 0 && out.numel() == total, "jpeg: out uint8 [base[B]]");
   a.out = out.data_ptr<uint8_t>();
   launch_jpeg_write(a, cur_stream());
@@ -1193,6 +1262,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("jpeg_write", &jpeg_write, nogil());
   m.def("jpeg_count_blocks", &jpeg_count_blocks, nogil());
   m.def("jpeg_write_blocks", &jpeg_write_blocks, nogil());
+  m.def("jpeg_count_opt", &jpeg_count_opt, nogil());
+  m.def("jpeg_write_opt", &jpeg_write_opt, nogil());
+  m.def("jpeg_count_blocks_opt", &jpeg_count_blocks_opt, nogil());
+  m.def("jpeg_write_blocks_opt", &jpeg_write_blocks_opt, nogil());
   m.def("jpeg_reconstruct", &jpeg_reconstruct, nogil());
   m.def("jpeg_entropy_decode", &jpeg_entropy_decode, nogil());
   m.def("jpeg_entropy_decode_chunked", &jpeg_entropy_decode_chunked, nogil());

@@ -211,11 +211,57 @@
 // workgroup, every loop is bounded by a size known at launch.  Device memory beyond coefficients
 // and payload: one word per block, one per interval, and the slots (208 bytes per block, of which
 // 4 bytes per block + 4 per interval are zeroed).
+//
+// OPTIMISED HUFFMAN TABLES (jpeg_format.symbol_counts / optimal_table are the numpy model,
+// jpeg_huff_opt.h the builder): with huffman = "optimized" every image of the batch is coded with,
+// and carries in its DHT, the four tables libjpeg's jpeg_gen_optimal_table (T.81 K.2) builds for
+// the image's own coefficients.  The coefficients, and so the decoded pixels, do not change.
+//
+//   Counts.  freq[t][s], t = DC luma, DC chroma, AC luma, AC chroma: how often the entropy coder
+//   of the byte contract emits symbol s of table t for the image: the category of every DC
+//   difference (against the DC predictor of the block coder, restart intervals included), every
+//   (run << 4) | size, ZRL and EOB.  32-bit words: an image has fewer than 2^31 coefficients
+//   (blocks * 64 < 2^31), larger ones are refused.
+//   Table from freq[0 .. 255]:
+//     1. freq[256] = 1, the reserved symbol: no code is all ones.
+//     2. codesize[0 .. 256] = 0, others[0 .. 256] = -1.
+//     3. Repeat: c1 = the index with the smallest non-zero freq, the largest index among equal
+//        values; c2 = the same search with c1 left out; if there is none, stop.
+//        freq[c1] += freq[c2]; freq[c2] = 0; codesize of c1 and of every index on its others chain
+//        + 1; the chain's end is linked to c2; codesize of c2 and of its chain + 1.
+//     4. bits[l] = the number of indices with codesize l, l up to 32 (a longer code is refused, as
+//        libjpeg refuses it; 2^31 symbols can reach it only with Fibonacci-like counts).
+//     5. For i = 32 .. 17, while bits[i] > 0: j = i - 2; while bits[j] == 0, j -= 1;
+//        bits[i] -= 2; bits[i - 1] += 1; bits[j + 1] += 2; bits[j] -= 1.
+//     6. From i = 16 down to the first bits[i] > 0: bits[i] -= 1 (the reserved symbol leaves).
+//     7. vals = for l = 1 .. 32, for j = 0 .. 255 ascending: j if codesize[j] == l.
+//   Codes are canonical from (bits[1 .. 16], vals) as in the ENTROPY DECODE CONTRACT.  A table
+//   lists only the symbols that occur (a table without any is 17 bytes of DHT).
+//   Header.  The segments and their order are the byte contract's, with one DHT segment holding
+//   the image's tables in the order DC luma, AC luma, DC chroma, AC chroma; its length, and so the
+//   header's, differs per image.
+//   Bounds.  Any code, a DC one included, can be 16 bits long: a block codes to at most
+//   16 + 11 + 63 * 26 = 1665 bits, and the block coder's slots are sized with that.
+//
+// Kernels, between transform and the coders' count pass: histogram (one lane per block in the
+// geometry of the bits kernel, the coder's own symbol walk with a counting sink, a HUFF_WORDS
+// histogram in LDS per workgroup flushed with integer atomicAdd into freq[B][HUFF_WORDS], zeroed
+// before) -> build (one workgroup per image, one wave per table; freq, codesize, others, bits in
+// LDS; the two searches of step 3 are wave reductions on the 64-bit key (freq, reversed index);
+// after a barrier the workgroup writes the image's (length << 16) | code words, its header =
+// the constant bytes before the DHT + its DHT + the constant bytes behind, and hdr_len[b]; a
+// refused table gives hdr_len[b] = 0, which the host reads with the image offsets).  Both coders
+// then read the image's words and hdr_len[b].  The interval kernel's 64 lanes and the block
+// kernels' BLK_LANES would straddle two images, so in this mode their grids get an image dimension
+// (blockIdx.y = image, blockIdx.x tiles the image's intervals / blocks): a workgroup holds one
+// image's table in LDS as before.  One launch per pass still, and at most 65535 images per call.
+// The host flow is unchanged: no copy or synchronisation is added.
 #include "common.h"
 #include "kernels.h"
 #include "jpeg_entropy_dec.h"
 #include "jpeg_entropy_sync.h"
 #include "jpeg_entropy_blk.h"
+#include "jpeg_huff_opt.h"
 
 namespace {
 
@@ -382,19 +428,35 @@ CM_DEVICE void put_ac(ByteSink<WRITE>& w, const uint32_t* ac, int& run, int val)
   run = 0;
 }
 
-// one lane per restart interval (gid = image * nint + interval)
+// Optimised tables: the image's own words and header length (a.ihuff is null with the standard
+// tables, and then every image shares a.huff and a.hdr_len).
+CM_DEVICE const uint32_t* image_huff(const JpegArgs& a, int b) {
+  return a.ihuff != nullptr ? a.ihuff + (long long)b * HUFF_WORDS : reinterpret_cast<const uint32_t*>(a.huff);
+}
+CM_DEVICE uint32_t image_hdr_len(const JpegArgs& a, int b) {
+  return a.ihuff != nullptr ? a.hdr_lens[b] : (uint32_t)a.hdr_len;
+}
+
+// one lane per restart interval (gid = image * nint + interval); with optimised tables
+// blockIdx.y is the image and blockIdx.x tiles its intervals
 template <bool WRITE>
 __global__ __launch_bounds__(64) void jpeg_entropy_kernel(JpegArgs a) {
   __shared__ uint32_t huff[HUFF_WORDS];
-  for (int i = threadIdx.x; i < HUFF_WORDS; i += 64) huff[i] = (uint32_t)a.huff[i];
+  const bool per_image = a.ihuff != nullptr;
+  const uint32_t* hsrc = image_huff(a, per_image ? (int)blockIdx.y : 0);
+  for (int i = threadIdx.x; i < HUFF_WORDS; i += 64) huff[i] = hsrc[i];
   __syncthreads();
-  const long long gid = (long long)blockIdx.x * 64 + threadIdx.x;
+  long long gid = (long long)blockIdx.x * 64 + threadIdx.x;
+  if (per_image) {
+    if (gid >= a.nint) return;
+    gid += (long long)blockIdx.y * a.nint;
+  }
   if (gid >= (long long)a.B * a.nint) return;
   const int b = (int)(gid / a.nint), it = (int)(gid % a.nint);
   const int mcus = a.mx * a.my;
   const int m0 = it * a.restart, m1 = min(m0 + a.restart, mcus);
   ByteSink<WRITE> w;
-  if (WRITE) w.out = a.out + a.base[b] + a.hdr_len + a.offs[gid];
+  if (WRITE) w.out = a.out + a.base[b] + image_hdr_len(a, b) + a.offs[gid];
   const uint4* p = reinterpret_cast<const uint4*>(a.coef + ((long long)b * mcus + m0) * a.nb * 64);
   int p0 = 0, p1 = 0, p2 = 0;
   for (int m = m0; m < m1; ++m) {
@@ -468,7 +530,7 @@ __global__ __launch_bounds__(256) void jpeg_scan_image_kernel(JpegArgs a) {
     running += tot;
     __syncthreads();
   }
-  if (tid == 0) a.base[1 + b] = (uint32_t)a.hdr_len + running;
+  if (tid == 0) a.base[1 + b] = image_hdr_len(a, b) + running;
 }
 
 // over the batch, one wave: base[1 + i] (image sizes) -> inclusive scan in place, base[0] = 0
@@ -487,7 +549,65 @@ __global__ __launch_bounds__(64) void jpeg_scan_batch_kernel(JpegArgs a) {
 
 __global__ __launch_bounds__(256) void jpeg_header_kernel(JpegArgs a) {
   uint8_t* dst = a.out + a.base[blockIdx.x];
+  if (a.ihuff != nullptr) {                              // the image's own header, built with its tables
+    const uint8_t* src = a.hdrs + (long long)blockIdx.x * a.hdr_cap;
+    const int n = min((int)a.hdr_lens[blockIdx.x], a.hdr_cap);
+    for (int i = threadIdx.x; i < n; i += 256) dst[i] = src[i];
+    return;
+  }
   for (int i = threadIdx.x; i < a.hdr_len; i += 256) dst[i] = a.header[i];
+}
+
+// ---------------------------------------------------------------------------------- optimised Huffman tables
+constexpr int HUFF_BASE[4] = {0, 16, 32, 32 + 256};    // DC luma, DC chroma, AC luma, AC chroma in HUFF_WORDS
+constexpr int HUFF_COUNT_LANES = 256;                   // = BLK_LANES: the geometry of the bits kernel
+
+// One lane per block of image blockIdx.y: the coder's symbol walk with the counting sink into the
+// workgroup's LDS histogram, then one integer atomicAdd per non-zero word into freq[image].
+__global__ __launch_bounds__(HUFF_COUNT_LANES) void jpeg_huff_count_kernel(JpegArgs a) {
+  __shared__ uint32_t hist[HUFF_WORDS];
+  for (int i = threadIdx.x; i < HUFF_WORDS; i += HUFF_COUNT_LANES) hist[i] = 0u;
+  __syncthreads();
+  const long long per_img = (long long)a.mx * a.my * a.nb;
+  const long long r = (long long)blockIdx.x * HUFF_COUNT_LANES + threadIdx.x;
+  const int b = blockIdx.y;
+  if (r < per_img) {
+    const long long m = r / a.nb;
+    const int blk = (int)(r % a.nb);
+    const int16_t* img = a.coef + (long long)b * per_img * 64;
+    const bool luma = blk < a.nb - 2;
+    jpeg_blk_count(img + r * 64, jpeg_blk_pred(img, m, blk, a.nb, a.restart), hist + (luma ? 0 : 16),
+                   hist + 32 + (luma ? 0 : 256));
+  }
+  __syncthreads();
+  uint32_t* freq = a.freq + (long long)b * HUFF_WORDS;
+  for (int i = threadIdx.x; i < HUFF_WORDS; i += HUFF_COUNT_LANES)
+    if (hist[i] != 0u) atomicAdd(freq + i, hist[i]);
+}
+
+// One workgroup per image, wave t builds table t (jpeg_huff_opt.h) in LDS; then the workgroup
+// writes the image's code words, its header and its header length (0: a table was refused).
+__global__ __launch_bounds__(256) void jpeg_huff_build_kernel(JpegArgs a) {
+  __shared__ JpegHuffWork work[4];
+  const int b = blockIdx.x, tid = threadIdx.x, t = tid >> 6, lane = tid & 63;
+  const int base = t == 0 ? HUFF_BASE[0] : (t == 1 ? HUFF_BASE[1] : (t == 2 ? HUFF_BASE[2] : HUFF_BASE[3]));
+  const int nslots = t < 2 ? 16 : 256;
+  JpegHuffWork& w = work[t];
+  const uint32_t* freq = a.freq + (long long)b * HUFF_WORDS + base;
+  for (int i = lane; i < JPEG_HUFF_SYMS; i += 64) w.freq[i] = i < nslots ? freq[i] : 0u;
+  jpeg_huff_sync();
+  jpeg_huff_build(w, lane);
+  jpeg_huff_assign(w, a.ihuff + (long long)b * HUFF_WORDS + base, nslots, lane);
+  __syncthreads();
+  const int pre = a.hdr_split, suf = a.hdr_len - a.hdr_split;
+  uint8_t* dst = a.hdrs + (long long)b * a.hdr_cap;
+  for (int i = tid; i < pre; i += 256) dst[i] = a.header[i];
+  const uint32_t room = (uint32_t)max(a.hdr_cap - pre - suf, 0);
+  const uint32_t dht = jpeg_huff_dht(work, dst + pre, room, tid, 256);
+  const bool ok = dht <= room && (work[0].bad | work[1].bad | work[2].bad | work[3].bad) == 0u;
+  if (ok)
+    for (int i = tid; i < suf; i += 256) dst[pre + dht + i] = a.header[pre + i];
+  if (tid == 0) a.hdr_lens[b] = ok ? (uint32_t)pre + dht + (uint32_t)suf : 0u;
 }
 
 // ---------------------------------------------------------------------------------- reconstruct
@@ -889,10 +1009,16 @@ constexpr int BLK_LANES = 256;
 // scalars.
 __global__ __launch_bounds__(BLK_LANES) void jpeg_blk_bits_kernel(JpegArgs a, JpegBlkArgs k) {
   __shared__ uint32_t huff[HUFF_WORDS];
-  for (int i = threadIdx.x; i < HUFF_WORDS; i += BLK_LANES) huff[i] = (uint32_t)a.huff[i];
+  const bool per_image = a.ihuff != nullptr;             // blockIdx.y = image, blockIdx.x tiles its blocks
+  const uint32_t* hsrc = image_huff(a, per_image ? (int)blockIdx.y : 0);
+  for (int i = threadIdx.x; i < HUFF_WORDS; i += BLK_LANES) huff[i] = hsrc[i];
   __syncthreads();
   const long long per_img = (long long)a.mx * a.my * a.nb;
-  const long long g = (long long)blockIdx.x * BLK_LANES + threadIdx.x;
+  long long g = (long long)blockIdx.x * BLK_LANES + threadIdx.x;
+  if (per_image) {
+    if (g >= per_img) return;
+    g += (long long)blockIdx.y * per_img;
+  }
   if (g >= (long long)a.B * per_img) return;
   const long long r = g % per_img, m = r / a.nb;
   const int blk = (int)(r % a.nb);
@@ -947,11 +1073,17 @@ __global__ __launch_bounds__(1024) void jpeg_blk_scan_kernel(JpegArgs a, JpegBlk
 // One lane per block again: the same coder, storing at the block's bit offset.
 __global__ __launch_bounds__(BLK_LANES) void jpeg_blk_pack_kernel(JpegArgs a, JpegBlkArgs k) {
   __shared__ uint32_t huff[HUFF_WORDS];
-  for (int i = threadIdx.x; i < HUFF_WORDS; i += BLK_LANES) huff[i] = (uint32_t)a.huff[i];
+  const bool per_image = a.ihuff != nullptr;             // as in the bits kernel
+  const uint32_t* hsrc = image_huff(a, per_image ? (int)blockIdx.y : 0);
+  for (int i = threadIdx.x; i < HUFF_WORDS; i += BLK_LANES) huff[i] = hsrc[i];
   __syncthreads();
   const int mcus = a.mx * a.my;
   const long long per_img = (long long)mcus * a.nb;
-  const long long g = (long long)blockIdx.x * BLK_LANES + threadIdx.x;
+  long long g = (long long)blockIdx.x * BLK_LANES + threadIdx.x;
+  if (per_image) {
+    if (g >= per_img) return;
+    g += (long long)blockIdx.y * per_img;
+  }
   if (g >= (long long)a.B * per_img) return;
   const long long r = g % per_img, m = r / a.nb;
   const int blk = (int)(r % a.nb);
@@ -987,7 +1119,7 @@ __global__ __launch_bounds__(1024) void jpeg_blk_stuff_kernel(JpegArgs a, JpegBl
     bad = true;
   }
   const uint32_t npiece = (ubytes + JPEG_BLK_PIECE - 1u) / JPEG_BLK_PIECE;
-  const uint32_t dst = WRITE ? a.base[b] + (uint32_t)a.hdr_len + a.offs[gid] : 0u;
+  const uint32_t dst = WRITE ? a.base[b] + image_hdr_len(a, b) + a.offs[gid] : 0u;
   uint32_t running = 0;
   for (uint32_t p0 = 0; p0 < npiece; p0 += (uint32_t)n) {
     const uint32_t p = p0 + (uint32_t)t;
@@ -1022,6 +1154,23 @@ __global__ __launch_bounds__(1024) void jpeg_blk_stuff_kernel(JpegArgs a, JpegBl
 }  // namespace
 
 int jpeg_blk_max_bits() { return (int)JPEG_BLK_MAX_BITS; }
+int jpeg_blk_max_bits_optimized() { return (int)JPEG_BLK_MAX_BITS_OPT; }
+
+// Optimised tables, behind the transform: zero freq, histogram, build (fills ihuff, hdrs, hdr_lens).
+static void launch_jpeg_huff_opt(const JpegArgs& a, hipStream_t s) {
+  launch_zero(a.freq, (size_t)a.B * HUFF_WORDS * sizeof(uint32_t), s);
+  const long long per_img = (long long)a.mx * a.my * a.nb;
+  const unsigned hg = (unsigned)((per_img + HUFF_COUNT_LANES - 1) / HUFF_COUNT_LANES);
+  hipLaunchKernelGGL(jpeg_huff_count_kernel, dim3(hg, (unsigned)a.B), dim3(HUFF_COUNT_LANES), 0, s, a);
+  hipLaunchKernelGGL(jpeg_huff_build_kernel, dim3((unsigned)a.B), dim3(256), 0, s, a);
+}
+
+// grid of a one-lane-per-item kernel: over the batch, or (optimised tables) per image with
+// blockIdx.y = image
+static dim3 item_grid(const JpegArgs& a, long long per_image, int lanes) {
+  if (a.ihuff != nullptr) return dim3((unsigned)((per_image + lanes - 1) / lanes), (unsigned)a.B);
+  return dim3((unsigned)((per_image * a.B + lanes - 1) / lanes));
+}
 
 static int blk_threads(long long items) {
   const long long t = (items + 63) / 64 * 64;
@@ -1034,12 +1183,13 @@ void launch_jpeg_count_blocks(const JpegArgs& a, const JpegBlkArgs& k, hipStream
   const unsigned tg = (unsigned)((mcus + TR_WAVES - 1) / TR_WAVES);
   if (a.nb == 6) hipLaunchKernelGGL(jpeg_transform_kernel<true>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
   else hipLaunchKernelGGL(jpeg_transform_kernel<false>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
-  const unsigned bg = (unsigned)((mcus * a.nb + BLK_LANES - 1) / BLK_LANES);
+  if (a.ihuff != nullptr) launch_jpeg_huff_opt(a, s);
+  const dim3 bg = item_grid(a, (long long)a.mx * a.my * a.nb, BLK_LANES);
   const unsigned ig = (unsigned)((long long)a.B * a.nint);
   const long long per = (long long)(a.restart < a.mx * a.my ? a.restart : a.mx * a.my) * a.nb;   // blocks per interval
-  hipLaunchKernelGGL(jpeg_blk_bits_kernel, dim3(bg), dim3(BLK_LANES), 0, s, a, k);
+  hipLaunchKernelGGL(jpeg_blk_bits_kernel, bg, dim3(BLK_LANES), 0, s, a, k);
   hipLaunchKernelGGL(jpeg_blk_scan_kernel, dim3(ig), dim3(blk_threads(per)), 0, s, a, k);
-  hipLaunchKernelGGL(jpeg_blk_pack_kernel, dim3(bg), dim3(BLK_LANES), 0, s, a, k);
+  hipLaunchKernelGGL(jpeg_blk_pack_kernel, bg, dim3(BLK_LANES), 0, s, a, k);
   // pieces per interval: sized for an eighth of the worst case, longer strings take more tiles
   const int st = blk_threads(((long long)k.stride * 4 / JPEG_BLK_PIECE + 7) / 8);
   hipLaunchKernelGGL(jpeg_blk_stuff_kernel<false>, dim3(ig), dim3(st), 0, s, a, k);
@@ -1060,15 +1210,14 @@ void launch_jpeg_count(const JpegArgs& a, hipStream_t s) {
   const unsigned tg = (unsigned)((mcus + TR_WAVES - 1) / TR_WAVES);
   if (a.nb == 6) hipLaunchKernelGGL(jpeg_transform_kernel<true>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
   else hipLaunchKernelGGL(jpeg_transform_kernel<false>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
-  const unsigned eg = (unsigned)(((long long)a.B * a.nint + 63) / 64);
-  hipLaunchKernelGGL(jpeg_entropy_kernel<false>, dim3(eg), dim3(64), 0, s, a);
+  if (a.ihuff != nullptr) launch_jpeg_huff_opt(a, s);
+  hipLaunchKernelGGL(jpeg_entropy_kernel<false>, item_grid(a, a.nint, 64), dim3(64), 0, s, a);
   hipLaunchKernelGGL(jpeg_scan_image_kernel, dim3(a.B), dim3(256), 0, s, a);
   hipLaunchKernelGGL(jpeg_scan_batch_kernel, dim3(1), dim3(64), 0, s, a);
 }
 
 void launch_jpeg_write(const JpegArgs& a, hipStream_t s) {
-  const unsigned eg = (unsigned)(((long long)a.B * a.nint + 63) / 64);
-  hipLaunchKernelGGL(jpeg_entropy_kernel<true>, dim3(eg), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(jpeg_entropy_kernel<true>, item_grid(a, a.nint, 64), dim3(64), 0, s, a);
   hipLaunchKernelGGL(jpeg_header_kernel, dim3(a.B), dim3(256), 0, s, a);
 }
 

@@ -11,7 +11,8 @@
 // The unstuffed string of an interval lives in 32-bit words, MSB first: bit p of the string is bit
 // 31 - (p & 31) of word p >> 5, byte i is bits 31 - 8 (i & 3) .. 24 - 8 (i & 3) of word i >> 2.
 //
-// Both forms of a routine are one template (count / write), so the two passes cannot disagree.
+// Both forms of a routine are one template (count / write), so the two passes cannot disagree; the
+// symbol walk has a third form that only counts its symbols (the histogram of the optimised tables).
 // Memory safety: a word is stored or merged only at an index below `nwords`, a payload byte only
 // at an index below `out_size`, a scratch word is read only below `nwords`; a refused index sets
 // `bad` and nothing is written.
@@ -88,6 +89,11 @@ struct JpegBlkSink {
       }
     }
   }
+  // a symbol of table `tab` followed by its `nbits` value bits
+  JPEG_BLK_FN void sym(const uint32_t* tab, int index, uint32_t bits, int nbits) {
+    const uint32_t h = tab[index];
+    put(((h & 0xffffu) << nbits) | bits, (int)(h >> 16) + nbits);
+  }
   // after the block's last symbol; `last`: the block ends its interval, whose last byte is padded
   // with 1-bits (bit_offset + pos is the interval's bit count)
   JPEG_BLK_FN void finish(uint32_t bit_offset, bool last) {
@@ -105,30 +111,41 @@ struct JpegBlkSink {
   }
 };
 
-template <bool WRITE>
-JPEG_BLK_FN void jpeg_blk_ac(JpegBlkSink<WRITE>& w, const uint32_t* ac, int& run, int val) {
+// The counting sink: the third form of the coder (OPTIMISED HUFFMAN TABLES, jpeg.hip's header
+// comment).  Its "tables" are histograms in the same layout, and a symbol adds one to its word.
+struct JpegBlkCount {
+  JPEG_BLK_FN void sym(uint32_t* tab, int index, uint32_t, int) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    atomicAdd(tab + index, 1u);
+#else
+    ++tab[index];
+#endif
+  }
+};
+
+template <class Sink, class Tab>
+JPEG_BLK_FN void jpeg_blk_ac(Sink& w, Tab ac, int& run, int val) {
   if (val == 0) {
     ++run;
     return;
   }
   while (run >= 16) {
-    const uint32_t z = ac[0xF0];
-    w.put(z & 0xffffu, (int)(z >> 16));
+    w.sym(ac, 0xF0, 0u, 0);
     run -= 16;
   }
   const int a = val < 0 ? -val : val;
   const int cat = 32 - __builtin_clz((unsigned)a);
   const uint32_t bits = (uint32_t)(val < 0 ? val - 1 : val) & ((1u << cat) - 1u);
-  const uint32_t h = ac[((run << 4) | cat) & 255];
-  w.put(((h & 0xffffu) << cat) | bits, (int)(h >> 16) + cat);
+  w.sym(ac, ((run << 4) | cat) & 255, bits, cat);
   run = 0;
 }
 
-// One block (64 zig-zag coefficients, 16-byte aligned) through the coder of the byte contract.
-// dc / ac: the (length << 16) | code tables of its component.  The bit count is w.pos.
-template <bool WRITE>
-JPEG_BLK_FN void jpeg_blk_code(const int16_t* blk, int pred, const uint32_t* dc, const uint32_t* ac,
-                               JpegBlkSink<WRITE>& w) {
+// One block (64 zig-zag coefficients, 16-byte aligned) through the symbol walk of the byte
+// contract: the DC category of the difference, then (run << 4) | size, ZRL and EOB, each handed
+// to the sink with its table, its value bits and their count.  Counting, measuring and storing
+// are this one walk with three sinks, so they cannot disagree.
+template <class Sink, class Tab>
+JPEG_BLK_FN void jpeg_blk_walk(const int16_t* blk, int pred, Tab dc, Tab ac, Sink& w) {
   const uint8_t* src = static_cast<const uint8_t*>(__builtin_assume_aligned(blk, 16));
   int run = 0;
 #pragma unroll 1
@@ -141,8 +158,7 @@ JPEG_BLK_FN void jpeg_blk_code(const int16_t* blk, int pred, const uint32_t* dc,
       const int a = d < 0 ? -d : d;
       const int cat = a ? 32 - __builtin_clz((unsigned)a) : 0;
       const uint32_t bits = (uint32_t)(d < 0 ? d - 1 : d) & ((1u << cat) - 1u);
-      const uint32_t h = dc[cat & 15];
-      w.put(((h & 0xffffu) << cat) | bits, (int)(h >> 16) + cat);
+      w.sym(dc, cat & 15, bits, cat);
       jpeg_blk_ac(w, ac, run, (int)(int16_t)(wd[0] >> 16));
 #pragma unroll
       for (int j = 2; j < 8; ++j) jpeg_blk_ac(w, ac, run, (int)(int16_t)((wd[j >> 1] >> (16 * (j & 1))) & 0xffffu));
@@ -153,7 +169,21 @@ JPEG_BLK_FN void jpeg_blk_code(const int16_t* blk, int pred, const uint32_t* dc,
       for (int j = 0; j < 8; ++j) jpeg_blk_ac(w, ac, run, (int)(int16_t)((wd[j >> 1] >> (16 * (j & 1))) & 0xffffu));
     }
   }
-  if (run > 0) w.put(ac[0] & 0xffffu, (int)(ac[0] >> 16));   // EOB
+  if (run > 0) w.sym(ac, 0, 0u, 0);   // EOB
+}
+
+// The coder: dc / ac are the (length << 16) | code tables of the block's component; the bit count
+// is w.pos.
+template <bool WRITE>
+JPEG_BLK_FN void jpeg_blk_code(const int16_t* blk, int pred, const uint32_t* dc, const uint32_t* ac,
+                               JpegBlkSink<WRITE>& w) {
+  jpeg_blk_walk(blk, pred, dc, ac, w);
+}
+
+// The histogram: dc / ac are the block's component's rows of a HUFF_WORDS histogram.
+JPEG_BLK_FN void jpeg_blk_count(const int16_t* blk, int pred, uint32_t* dc, uint32_t* ac) {
+  JpegBlkCount w;
+  jpeg_blk_walk(blk, pred, dc, ac, w);
 }
 
 // One stuffing piece: the unstuffed bytes b0 .. b1 - 1 (b0 a multiple of 4) of the string in

@@ -230,6 +230,14 @@ struct JpegArgs {
   // launch_jpeg_reconstruct (decode contract in jpeg.hip's header comment)
   uint8_t* planes = nullptr;         // scratch: Y [B][yh][yw], Cb, Cr [B][8 my][8 mx]; yh x yw = 16 my x 16 mx (4:2:0) or 8 my x 8 mx
   uint8_t* dec = nullptr;            // [B][H][W][3] the pixels a libjpeg decoder gives for coef
+  // optimised Huffman tables (section of that name in jpeg.hip's header comment; jpeg_huff_opt.h).
+  // ihuff == nullptr: the standard tables, and none of these is read.  Otherwise header holds the
+  // bytes before the DHT segment (hdr_split of them) followed by those behind it, B <= 65535.
+  uint32_t* freq = nullptr;          // [B][2*16 + 2*256] symbol counts, the layout of huff
+  uint32_t* ihuff = nullptr;         // [B][2*16 + 2*256] every image's own (length << 16) | code words
+  uint8_t* hdrs = nullptr;           // [B][hdr_cap] every image's header
+  uint32_t* hdr_lens = nullptr;      // [B] its length (0: a table was refused); in work, behind base
+  int hdr_cap = 0, hdr_split = 0;
 };
 // transform + interval byte counts + scans: fills coef, lens, offs, base
 void launch_jpeg_count(const JpegArgs& a, hipStream_t s);
@@ -247,6 +255,7 @@ struct JpegBlkArgs {
                                      // by a refused payload index
 };
 int jpeg_blk_max_bits();
+int jpeg_blk_max_bits_optimized();   // with optimised tables (a.ihuff): stride is sized with this
 // transform + bits per block + scan per interval + pack + 0xFF count per piece + the scans of
 // launch_jpeg_count: fills coef, bits, ubits, scratch, err, lens, offs, base
 void launch_jpeg_count_blocks(const JpegArgs& a, const JpegBlkArgs& k, hipStream_t s);

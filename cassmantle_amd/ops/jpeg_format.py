@@ -108,15 +108,36 @@ def _huff_codes(bits: Sequence[int], vals: Sequence[int]) -> Dict[int, Tuple[int
     return out
 
 
-@lru_cache(maxsize=None)
-def huff_table() -> np.ndarray:
-    """int32 [2*16 + 2*256]: ``(length << 16) | code`` per symbol for DC luma, DC chroma (16
-    slots each, 12 used), AC luma, AC chroma (256 each); 0 marks a symbol that has no code."""
+STANDARD_TABLES = (_DC_LUMA, _DC_CHROMA, _AC_LUMA, _AC_CHROMA)      # (bits, vals): DC luma, DC chroma, AC luma, AC chroma
+HUFF_BASES = (0, 16, 32, 32 + 256)     # first word of every table in huff_table()
+HUFFMAN_MODES = ("standard", "optimized")
+
+
+def _frozen_tables(tables):
+    """Four (bits, vals) as nested tuples (hashable), or None for the standard tables."""
+    if tables is None:
+        return None
+    tables = tuple((tuple(int(b) for b in bits), tuple(int(v) for v in vals)) for bits, vals in tables)
+    if len(tables) != 4 or any(len(bits) != 16 or sum(bits) != len(vals) for bits, vals in tables):
+        raise ValueError("jpeg: tables = four (bits[16], vals): DC luma, DC chroma, AC luma, AC chroma")
+    return tables
+
+
+@lru_cache(maxsize=64)
+def _huff_table(tables) -> np.ndarray:
     t = np.zeros(2 * 16 + 2 * 256, dtype=np.int32)
-    for base, (bits, vals) in ((0, _DC_LUMA), (16, _DC_CHROMA), (32, _AC_LUMA), (32 + 256, _AC_CHROMA)):
+    for base, (bits, vals) in zip(HUFF_BASES, STANDARD_TABLES if tables is None else tables):
         for sym, (code, length) in _huff_codes(bits, vals).items():
             t[base + sym] = (length << 16) | code
     return t
+
+
+def huff_table(tables=None) -> np.ndarray:
+    """int32 [2*16 + 2*256]: ``(length << 16) | code`` per symbol for DC luma, DC chroma (16
+    slots each, 12 used), AC luma, AC chroma (256 each); 0 marks a symbol that has no code.
+    ``tables``: four ``(bits, vals)`` (DC luma, DC chroma, AC luma, AC chroma) in place of the
+    standard ones."""
+    return _huff_table(_frozen_tables(tables))
 
 
 def geometry(H: int, W: int, sampling: str) -> Tuple[int, int, int, int]:
@@ -131,10 +152,28 @@ def _seg(marker: int, payload: bytes) -> bytes:
     return struct.pack(">BBH", 0xFF, marker, len(payload) + 2) + payload
 
 
-@lru_cache(maxsize=64)
-def header(H: int, W: int, quality: int, sampling: str, restart_mcus: int) -> bytes:
+def header(H: int, W: int, quality: int, sampling: str, restart_mcus: int, tables=None) -> bytes:
     """SOI / APP0 / DQT / SOF0 / DHT / DRI / SOS for one image (the entropy-coded data and EOI
-    follow)."""
+    follow).  ``tables``: four ``(bits, vals)`` (DC luma, DC chroma, AC luma, AC chroma) written into
+    the one DHT segment in place of the standard ones, in the same order (DC luma, AC luma, DC
+    chroma, AC chroma)."""
+    pre, suf = header_parts(H, W, quality, sampling, restart_mcus)
+    return pre + dht_segment(tables) + suf
+
+
+def dht_segment(tables=None) -> bytes:
+    """The DHT segment of four ``(bits, vals)`` (default: the standard tables)."""
+    t = STANDARD_TABLES if tables is None else _frozen_tables(tables)
+    dht = b""
+    for tc_th, (bits, vals) in ((0x00, t[0]), (0x10, t[2]), (0x01, t[1]), (0x11, t[3])):
+        dht += bytes([tc_th]) + bytes(bits) + bytes(vals)
+    return _seg(0xC4, dht)
+
+
+@lru_cache(maxsize=64)
+def header_parts(H: int, W: int, quality: int, sampling: str, restart_mcus: int) -> Tuple[bytes, bytes]:
+    """(the header bytes before the DHT segment, those after it): the same for every image of a
+    geometry, whatever its Huffman tables."""
     if not (0 < H < 65536 and 0 < W < 65536):
         raise ValueError("jpeg: image sides must be in 1..65535")
     if not 0 <= restart_mcus < 65536:
@@ -146,14 +185,11 @@ def header(H: int, W: int, quality: int, sampling: str, restart_mcus: int) -> by
     out += _seg(0xDB, bytes([0]) + bytes(lq[i] for i in ZIGZAG) + bytes([1]) + bytes(cq[i] for i in ZIGZAG))
     hv = 0x22 if sampling == "420" else 0x11
     out += _seg(0xC0, struct.pack(">BHHB", 8, H, W, 3) + bytes([1, hv, 0, 2, 0x11, 1, 3, 0x11, 1]))
-    dht = b""
-    for tc_th, (bits, vals) in ((0x00, _DC_LUMA), (0x10, _AC_LUMA), (0x01, _DC_CHROMA), (0x11, _AC_CHROMA)):
-        dht += bytes([tc_th]) + bytes(bits) + bytes(vals)
-    out += _seg(0xC4, dht)
+    suf = b""
     if restart_mcus:
-        out += _seg(0xDD, struct.pack(">H", restart_mcus))
-    out += _seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
-    return out
+        suf += _seg(0xDD, struct.pack(">H", restart_mcus))
+    suf += _seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
+    return out, suf
 
 
 # ----------------------------------------------------------------------------- transform
@@ -235,9 +271,10 @@ def _category(v: int) -> int:
     return abs(v).bit_length()
 
 
-def entropy(coef: np.ndarray, restart_mcus: int):
-    """int16 [mcus, nb, 64] -> (scan bytes with RSTn markers, stats)."""
-    huff = huff_table()
+def entropy(coef: np.ndarray, restart_mcus: int, tables=None):
+    """int16 [mcus, nb, 64] -> (scan bytes with RSTn markers, stats).  ``tables``: four
+    ``(bits, vals)`` in place of the standard Huffman tables."""
+    huff = huff_table(tables)
     mcus, nb, _ = coef.shape
     per = restart_mcus if restart_mcus else mcus
     nint = (mcus + per - 1) // per
@@ -354,7 +391,8 @@ def _block_code(blk, pred: int, luma: bool, huff, stats: dict):
     return acc, n
 
 
-def entropy_blocks(coef: np.ndarray, restart_mcus: int, stuff_chunk: int = BLK_STUFF_CHUNK, stats: dict = None):
+def entropy_blocks(coef: np.ndarray, restart_mcus: int, stuff_chunk: int = BLK_STUFF_CHUNK, stats: dict = None,
+                   tables=None):
     """What :func:`entropy` returns, computed the way the BLOCK-PARALLEL ENTROPY CODER says: per
     restart interval the bit length of every block (DC difference against :func:`dc_predictors`),
     the exclusive scan of the lengths, every block's bits packed at its offset into the unstuffed
@@ -365,10 +403,11 @@ def entropy_blocks(coef: np.ndarray, restart_mcus: int, stuff_chunk: int = BLK_S
     lengths), ``max_starts_per_word`` (blocks starting in one 32-bit word of an interval's string),
     ``ff_two_blocks`` (unstuffed 0xFF bytes with a block boundary inside), ``ff_interval_end``
     (intervals whose last unstuffed byte is 0xFF), ``ff_piece_end`` (0xFF bytes that are the last
-    byte of a full piece), ``ff_pairs`` (two consecutive unstuffed 0xFF bytes), ``unstuffed`` (bytes)."""
+    byte of a full piece), ``ff_pairs`` (two consecutive unstuffed 0xFF bytes), ``unstuffed`` (bytes).
+    ``tables``: four ``(bits, vals)`` in place of the standard Huffman tables."""
     if int(stuff_chunk) != stuff_chunk or stuff_chunk < 1:
         raise ValueError("jpeg: stuff_chunk must be a positive integer")
-    huff = huff_table()
+    huff = huff_table(tables)
     mcus, nb, _ = coef.shape
     per = restart_mcus if restart_mcus else mcus
     nint = (mcus + per - 1) // per
@@ -421,11 +460,16 @@ def entropy_blocks(coef: np.ndarray, restart_mcus: int, stuff_chunk: int = BLK_S
 
 
 def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: int = 4,
-                return_stats: bool = False):
+                return_stats: bool = False, huffman: str = "standard"):
     """Baseline JPEG of uint8 ``[B, H, W, 3]`` (or ``[H, W, 3]``) images: one byte string per
     image.  ``restart_mcus`` MCUs per restart interval (0: no DRI, one interval).  With
     ``return_stats`` also a dict per image: ``stuffed`` (0xFF bytes that needed a stuffed zero),
-    ``zrl`` (ZRL symbols), ``max_dc_cat`` (largest DC difference category), ``intervals``."""
+    ``zrl`` (ZRL symbols), ``max_dc_cat`` (largest DC difference category), ``intervals``.
+    ``huffman="optimized"``: every image is coded with, and carries in its DHT, the tables
+    :func:`optimal_table` builds from its own :func:`symbol_counts` (what libjpeg's ``optimize``
+    writes for those coefficients)."""
+    if huffman not in HUFFMAN_MODES:
+        raise ValueError(f"jpeg_encode: huffman must be one of {HUFFMAN_MODES}, not {huffman!r}")
     arr = images.detach().cpu().numpy() if hasattr(images, "detach") else np.asarray(images)
     if arr.ndim == 3:
         arr = arr[None]
@@ -433,12 +477,137 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
         raise ValueError("jpeg_encode: uint8 [B, H, W, 3] or [H, W, 3] expected")
     _, H, W, _ = arr.shape
     hdr = header(H, W, int(quality), sampling, int(restart_mcus))
+    if huffman == "optimized":
+        _, nb, mx, my = geometry(H, W, sampling)
+        check_count_range(mx * my * nb)
     outs, stats = [], []
     for img in arr:
-        scan, st = entropy(coefficients(img, int(quality), sampling), int(restart_mcus))
+        coef = coefficients(img, int(quality), sampling)
+        tables = None
+        if huffman == "optimized":
+            tables = optimal_tables(symbol_counts(coef, int(restart_mcus)))
+            hdr = header(H, W, int(quality), sampling, int(restart_mcus), tables)
+        scan, st = entropy(coef, int(restart_mcus), tables)
         outs.append(hdr + scan + b"\xff\xd9")
         stats.append(st)
     return (outs, stats) if return_stats else outs
+
+
+# ----------------------------------------------------------------------------- optimised Huffman tables
+# The tables libjpeg builds for an image's own symbols (jpeg_gen_optimal_table, T.81 K.2): the
+# OPTIMISED HUFFMAN TABLES section of jpeg.hip's header comment; ops/csrc/jpeg_huff_opt.h is the
+# routine the build kernel and the host program compile.
+def block_bits_bound_optimized() -> int:
+    """The most bits one block can code to with tables of its image's own: any code, a DC one
+    included, can be 16 bits long: 16 + 11 value bits, and 63 times 16 + 10."""
+    return 16 + 11 + 63 * (16 + 10)
+
+
+def check_count_range(blocks: int) -> None:
+    """Symbol counts are 32-bit words: an image has fewer than 2^31 coefficients."""
+    if int(blocks) * 64 >= 1 << 31:
+        raise ValueError("jpeg: optimised Huffman tables count symbols in 32-bit words: blocks * 64 must be below 2^31")
+
+
+def symbol_counts(coef: np.ndarray, restart_mcus: int) -> np.ndarray:
+    """int64 [4, 257]: how often :func:`entropy` emits every symbol for int16 [mcus, nb, 64]
+    coefficients; rows DC luma, DC chroma, AC luma, AC chroma (column 256 stays 0: the reserved
+    symbol of :func:`optimal_table`).  DC: the category of the difference against
+    :func:`dc_predictors`; AC: ``(run << 4) | size``, ZRL (0xF0) per 16 zeros before a value, EOB
+    (0x00) when the block ends in zeros."""
+    mcus, nb, _ = coef.shape
+    check_count_range(mcus * nb)
+    freq = np.zeros((4, 257), dtype=np.int64)
+    c = coef.astype(np.int64)
+
+    def cat(v):
+        a = np.abs(v)
+        return np.where(a > 0, np.floor(np.log2(np.maximum(a, 1))).astype(np.int64) + 1, 0)
+    d = c[..., 0] - dc_predictors(coef, restart_mcus)
+    chroma = np.arange(nb) >= nb - 2
+    dcat = cat(d)
+    freq[0, :32] += np.bincount(dcat[:, ~chroma].ravel(), minlength=32)
+    freq[1, :32] += np.bincount(dcat[:, chroma].ravel(), minlength=32)
+    ac = c[..., 1:]
+    nz = ac != 0
+    pos = np.arange(1, 64)
+    # zig-zag position of the previous non-zero AC value (0: none) before every position
+    last = np.maximum.accumulate(np.where(nz, pos, 0), axis=-1)
+    prev = np.concatenate([np.zeros(last.shape[:-1] + (1,), dtype=np.int64), last[..., :-1]], axis=-1)
+    run = pos - prev - 1
+    for t, sel in ((2, ~chroma), (3, chroma)):
+        m = nz[:, sel]
+        r = run[:, sel][m]
+        freq[t, :256] += np.bincount(((r & 15) << 4) | cat(ac[:, sel][m]), minlength=256)
+        freq[t, 0xF0] += int((r >> 4).sum())
+        freq[t, 0x00] += int((last[:, sel][..., -1] != 63).sum())
+    return freq
+
+
+def code_sizes(freq) -> List[int]:
+    """Steps 1 - 3 of :func:`optimal_table`: the code length of the 257 indices (the reserved
+    symbol last) before the lengths are limited to 16; 0 for an index that does not occur."""
+    f = [int(v) for v in np.asarray(freq).ravel()[:256]]
+    f += [0] * (256 - len(f)) + [1]              # f[256]: the reserved symbol, no code is all ones
+    codesize = [0] * 257
+    others = [-1] * 257
+    while True:
+        c1, v = -1, 1 << 62
+        for i in range(257):
+            if f[i] and f[i] <= v:
+                v, c1 = f[i], i
+        c2, v = -1, 1 << 62
+        for i in range(257):
+            if f[i] and f[i] <= v and i != c1:
+                v, c2 = f[i], i
+        if c2 < 0:
+            break
+        f[c1] += f[c2]
+        f[c2] = 0
+        codesize[c1] += 1
+        while others[c1] >= 0:
+            c1 = others[c1]
+            codesize[c1] += 1
+        others[c1] = c2
+        codesize[c2] += 1
+        while others[c2] >= 0:
+            c2 = others[c2]
+            codesize[c2] += 1
+    return codesize
+
+
+def optimal_table(freq) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+    """``(bits[16], vals)`` of the Huffman table libjpeg builds for the symbol frequencies
+    ``freq[0..255]`` (``jpeg_gen_optimal_table``; the steps and tie rules: jpeg.hip's header
+    comment).  No symbol: an empty table."""
+    codesize = code_sizes(freq)
+    if max(codesize) > 32:
+        raise ValueError("jpeg: a Huffman code longer than 32 bits")
+    bits = [0] * 33
+    for i in range(257):
+        if codesize[i]:
+            bits[codesize[i]] += 1
+    for i in range(32, 16, -1):
+        while bits[i] > 0:
+            j = i - 2
+            while bits[j] == 0:
+                j -= 1
+            bits[i] -= 2
+            bits[i - 1] += 1
+            bits[j + 1] += 2
+            bits[j] -= 1
+    i = 16
+    while i > 0 and bits[i] == 0:
+        i -= 1
+    if i > 0:
+        bits[i] -= 1                             # the reserved symbol leaves
+    vals = [j for length in range(1, 33) for j in range(256) if codesize[j] == length]
+    return tuple(bits[1:17]), tuple(vals)
+
+
+def optimal_tables(freq) -> tuple:
+    """Four ``(bits, vals)`` from :func:`symbol_counts`' [4, 257]."""
+    return tuple(optimal_table(row) for row in np.asarray(freq))
 
 
 # ----------------------------------------------------------------------------- decode contract

@@ -104,11 +104,24 @@ def jpeg_restart(cfg: Config, width: int):
     return r or (int(width) + 15) // 16, entropy
 
 
+def jpeg_huffman(cfg: Config) -> str:
+    """``ModelConfig.jpeg_huffman`` (standard | optimized) for ops.jpeg_encode; an unknown value is
+    an error, not the default."""
+    h = str(cfg.model.jpeg_huffman).lower()
+    if h not in ("standard", "optimized"):
+        raise ValueError(f"jpeg_huffman={cfg.model.jpeg_huffman!r}: expected standard or optimized")
+    return h
+
+
 def _jpeg_encode_args(cfg: Config, width: int) -> dict:
-    """jpeg_restart as keyword arguments of ops.jpeg_encode; the default coder is not named, so
-    the default configuration makes the call it always made."""
+    """jpeg_restart and jpeg_huffman as keyword arguments of ops.jpeg_encode; the default coder and
+    the default tables are not named, so the default configuration makes the call it always made."""
     restart, entropy = jpeg_restart(cfg, width)
-    return {"restart_mcus": restart} if entropy == "interval" else {"restart_mcus": restart, "entropy": entropy}
+    kw = {"restart_mcus": restart} if entropy == "interval" else {"restart_mcus": restart, "entropy": entropy}
+    huffman = jpeg_huffman(cfg)
+    if huffman != "standard":
+        kw["huffman"] = huffman
+    return kw
 
 
 def _device_pixels(img, dev: str) -> torch.Tensor:
@@ -163,6 +176,7 @@ def build_blur_jpeg_fn(cfg: Config, device: Optional[str] = None):
         return None
     from .. import ops
     jpeg_restart(cfg, 16)                   # a bad jpeg_entropy / jpeg_restart_mcus raises here, not per request
+    jpeg_huffman(cfg)                       # and so does a bad jpeg_huffman
     if kernel == "pil":
         def blur_jpeg_exact(img, radii: Sequence[float], quality: int):
             x = _device_pixels(img, dev)
@@ -199,6 +213,7 @@ def build_content_jpeg_fn(cfg: Config, device: Optional[str] = None):
     from .. import ops
     from ..game.content import DeviceImage
     jpeg_restart(cfg, 16)                   # a bad jpeg_entropy / jpeg_restart_mcus raises here, not per request
+    jpeg_huffman(cfg)                       # and so does a bad jpeg_huffman
 
     def content_jpeg(img, quality: int):
         x = img.tensor.to(dev, non_blocking=False)

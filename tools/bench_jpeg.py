@@ -61,6 +61,17 @@ nothing else queued) of the encode's two launch groups on the same pixels: count
 the same kernel for both coders, + everything up to the image offsets) and write phase.
 
     python tools/bench_jpeg.py --entropy block [--content] [--jpeg_restart_mcus 0 4 -1] [--out profiles/jpeg_block.jsonl]
+
+``--huffman optimized`` compares ``jpeg_huffman=optimized`` (every image's own Huffman tables, built
+on the device) against the standard tables in the prewarm (default, with ``--blur-kernel pil`` for
+that blur) or the ``--content`` mode, for both entropy coders (interval at one MCU row, block
+without restart markers), standard and optimised rows interleaved ``--reps`` times after a warm-up
+of each; the yardstick is the standard row of the same run.  Per record: host wall time, CPU time,
+JPEG bytes; then per coder the device time (HIP events, nothing else queued) of the count phase
+with both tables: their difference is the histogram + table build (and the count pass reading an
+image's own table).
+
+    python tools/bench_jpeg.py --huffman optimized [--blur-kernel pil] [--content] [--out profiles/jpeg_huffman.jsonl]
 """
 import argparse
 import io
@@ -267,6 +278,113 @@ def block_main(a, emit) -> int:
                 nint = -(-((res + 15) // 16) ** 2 // restart)
                 rec.update(scratch_bytes_allocated=8 * pixels.shape[0] * nint, scratch_bytes_zeroed=0)
             emit(dict(rec, count_phase_device_ms=round(cnt, 4), write_phase_device_ms=round(wr, 4)))
+    return 0
+
+
+def count_phase_device_ms(batch, restart: int, entropy: str, optimized: bool, iters: int = 5) -> float:
+    """Device time (HIP events; nothing else is queued) of the count phase of ops.jpeg_encode on
+    ``batch``: transform (+ histogram + table build with ``optimized``) + the coder's count pass +
+    scans, in ms; ``restart`` 0 = no restart markers (block coder)."""
+    import torch
+    from cassmantle_amd import ops
+    from cassmantle_amd.ops import jpeg_format as jf
+    from cassmantle_amd.ops._ext import ext
+    B, H, W, _ = batch.shape
+    _, nb, mx, my = jf.geometry(H, W, "420")
+    per = min(restart, mx * my) if restart else mx * my
+    nint = -(-mx * my // per)
+    opt, sfx = (), ""
+    if optimized:
+        tables, header, split = ops._jpeg_opt_plan(batch.device, H, W, QUALITY, "420", restart)
+        opt = (torch.empty(2 * B * 544, device="cuda", dtype=torch.int32),
+               torch.empty(B * (header.numel() + 4 + 4 * (17 + 256)), device="cuda", dtype=torch.uint8), split)
+        sfx = "_opt"
+    else:
+        tables, header = ops._jpeg_plan(batch.device, H, W, QUALITY, "420", restart)
+    coef = torch.empty((B, mx * my, nb, 64), device="cuda", dtype=torch.int16)
+    block = entropy == "block"
+    work = torch.empty(2 * B * nint + B + 1 + int(block) + (B if optimized else 0), device="cuda", dtype=torch.int32)
+    if block:
+        bound = jf.block_bits_bound_optimized() if optimized else jf.block_bits_bound()
+        stride = (per * nb * bound + 31) // 32
+        blk = torch.empty(B * mx * my * nb + B * nint, device="cuda", dtype=torch.int32)
+        scratch = torch.empty(B * nint * stride, device="cuda", dtype=torch.int32)
+    best = 1e9
+    for _ in range(iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        if block:
+            getattr(ext(), "jpeg_count_blocks" + sfx)(batch, tables, header, coef, work, blk, scratch, stride, 1, restart, *opt)
+        else:
+            getattr(ext(), "jpeg_count" + sfx)(batch, tables, header, coef, work, 1, restart, *opt)
+        e1.record()
+        torch.cuda.synchronize()
+        best = min(best, e0.elapsed_time(e1))
+    return best
+
+
+def huffman_main(a, emit) -> int:
+    """--huffman optimized: the image's own Huffman tables against the standard ones (see the module text)."""
+    import torch
+    from cassmantle_amd import ops
+    from cassmantle_amd.config import Config
+    from cassmantle_amd.game.content import DeviceImage
+    from cassmantle_amd.game.imaging import encode_jpeg
+    from cassmantle_amd.runtime.factory import build_blur_fn, build_blur_jpeg_fn, build_content_jpeg_fn, jpeg_restart
+
+    def config(entropy, huffman):
+        c = Config()
+        c.model.gpu_jpeg = c.model.gpu_jpeg_content = True
+        if a.blur_kernel:
+            c.model.blur_kernel = a.blur_kernel
+        c.model.jpeg_entropy, c.model.jpeg_restart_mcus = entropy, (-1 if entropy == "block" else 0)
+        c.model.jpeg_huffman = huffman
+        return c
+
+    rows = [(e, h) for e in ("interval", "block") for h in ("standard", a.huffman)]
+    for res in a.res:
+        img = source_image(res).copy()
+        jpeg = encode_jpeg(img, QUALITY)
+        dimg = DeviceImage(torch.from_numpy(img).cuda())
+        dimg.host()
+        blur_fn = build_blur_fn(config("interval", "standard"), "cuda")
+        radii = [i * BUCKET for i in range(1, int(MAX_BLUR / BUCKET) + 1)]
+        mode = "content" if a.content else "prewarm"
+
+        def run(entropy, huffman, tag):
+            cfg = config(entropy, huffman)
+            rec = {"res": res, "mode": mode, "blur_kernel": cfg.model.blur_kernel, "entropy": entropy, "huffman": huffman,
+                   "restart_mcus": jpeg_restart(cfg, res)[0]}
+            if a.content:
+                fn = build_content_jpeg_fn(cfg, "cuda")
+                d = DeviceImage(dimg.tensor)
+                torch.cuda.synchronize()
+                w0, c0 = time.perf_counter(), time.process_time()
+                data, _ = fn(d, QUALITY)
+                torch.cuda.synchronize()
+                wall, cpu = time.perf_counter() - w0, time.process_time() - c0
+                outs = [data]
+            else:
+                n, wall, cpu, got = prewarm_once(blur_fn, build_blur_jpeg_fn(cfg, "cuda"), dimg, jpeg, tag)
+                outs = [v for r, v in sorted(got.items()) if r > 0]
+                rec["buckets"] = n
+            rec.update(wall_ms=round(wall * 1e3, 3), cpu_ms=round(cpu * 1e3, 3), jpeg_bytes=sum(len(v) for v in outs))
+            return rec, outs
+
+        for entropy, huffman in rows:                   # warm-up of each
+            run(entropy, huffman, f"warm-{entropy}-{huffman}")
+        for rep in range(a.reps):
+            for entropy, huffman in rows:
+                emit(dict(run(entropy, huffman, f"{entropy}-{huffman}-{rep}")[0], rep=rep))
+        pixels = dimg.tensor[None].contiguous() if a.content else ops.gaussian_blur_pil(dimg.tensor, radii)
+        for entropy in ("interval", "block"):           # device time of the count phase, both tables
+            restart = jpeg_restart(config(entropy, "standard"), res)[0]
+            std = count_phase_device_ms(pixels, restart, entropy, False)
+            opt = count_phase_device_ms(pixels, restart, entropy, True)
+            emit({"res": res, "mode": mode, "entropy": entropy, "images": int(pixels.shape[0]),
+                  "count_phase_device_ms_standard": round(std, 4), "count_phase_device_ms_optimized": round(opt, 4),
+                  "histogram_and_build_device_ms": round(opt - std, 4)})
     return 0
 
 
@@ -570,6 +688,8 @@ def main(argv=None) -> int:
                     help="the prewarm comparison with blur_kernel=pil as a third row (see above)")
     ap.add_argument("--entropy", choices=["block"], default=None,
                     help="the block-parallel entropy coder against the interval coder, prewarm or --content (see above)")
+    ap.add_argument("--huffman", choices=["optimized"], default=None,
+                    help="the image's own Huffman tables against the standard ones, prewarm or --content (see above)")
     ap.add_argument("--jpeg_restart_mcus", type=int, nargs="+", default=[0, 4, -1],
                     help="--entropy block: the settings compared (0: one MCU row, -1: no restart markers)")
     a = ap.parse_args(argv)
@@ -594,8 +714,8 @@ def main(argv=None) -> int:
             sink.write(line + "\n")
             sink.flush()
 
-    if a.entropy:
-        rc = block_main(a, emit)
+    if a.entropy or a.huffman:
+        rc = huffman_main(a, emit) if a.huffman else block_main(a, emit)
         if sink:
             sink.close()
         return rc
