@@ -138,6 +138,10 @@ class ModelConfig:
     # image's own tables, built on the device: what PIL's optimize=True writes; the same pixels in
     # fewer bytes, profiles/jpeg_huffman.jsonl)
     jpeg_huffman: str = "standard"
+    # the forward transform of ops.jpeg_encode: matrix (the byte contract's own DCT, today's bytes)
+    # | libjpeg (libjpeg's edge rules, chroma mean, ISLOW DCT, dummy blocks and header layout: with
+    # jpeg_entropy=block and jpeg_restart_mcus=-1 the file PIL's save writes, byte for byte)
+    jpeg_transform: str = "matrix"
     # the content JPEG itself (radius 0, the bytes the content version hashes) encoded on the GPU
     # too, and its DECODED pixels (computed there from the same coefficients) registered as the
     # blur source: the image never crosses to the host, and masked bytes no longer depend on

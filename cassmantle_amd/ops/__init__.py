@@ -822,18 +822,18 @@ def gaussian_blur_pil(img, radii, out: Optional[torch.Tensor] = None):
     return res[0] if scalar else res
 
 
-_JPEG_PLANS: dict = {}     # (device, H, W, quality, sampling, restart_mcus) -> (tables, header) on the device
+_JPEG_PLANS: dict = {}     # (device, H, W, quality, sampling, restart_mcus, layout) -> (tables, header) on the device
 
 
-def _jpeg_plan(device, H: int, W: int, quality: int, sampling: str, restart_mcus: int):
+def _jpeg_plan(device, H: int, W: int, quality: int, sampling: str, restart_mcus: int, layout: str = "compact"):
     """The encoder's constant inputs on ``device``: int32 [128 + 544] quantisation | Huffman tables
-    and the uint8 header bytes (SOI .. SOS), uploaded once per key."""
+    and the uint8 header bytes (SOI .. SOS) in the header ``layout``, uploaded once per key."""
     from . import jpeg_format as jf
-    key = (device, H, W, quality, sampling, restart_mcus)
+    key = (device, H, W, quality, sampling, restart_mcus, layout)
     plan = _JPEG_PLANS.get(key)
     if plan is None:
         import numpy as np
-        hdr = jf.header(H, W, quality, sampling, restart_mcus)
+        hdr = jf.header(H, W, quality, sampling, restart_mcus, None, layout)
         lq, cq = jf.quant_tables(quality)
         tables = np.concatenate([np.asarray(lq + cq, dtype=np.int32), jf.huff_table()])
         if len(_JPEG_PLANS) >= 64:
@@ -845,27 +845,29 @@ def _jpeg_plan(device, H: int, W: int, quality: int, sampling: str, restart_mcus
 
 JPEG_ENTROPY_CODERS = ("interval", "block")
 JPEG_HUFFMAN_MODES = ("standard", "optimized")
-_JPEG_OPT_PLANS: dict = {}     # (device, H, W, quality, sampling, restart_mcus) -> (tables, header parts, split) on the device
+JPEG_TRANSFORMS = ("matrix", "libjpeg")
+_JPEG_OPT_PLANS: dict = {}     # (device, H, W, quality, sampling, restart_mcus, layout) -> (tables, header parts, split) on the device
 
 
-def _jpeg_opt_plan(device, H: int, W: int, quality: int, sampling: str, restart_mcus: int):
+def _jpeg_opt_plan(device, H: int, W: int, quality: int, sampling: str, restart_mcus: int, layout: str = "compact"):
     """The constant inputs of an encode with optimised Huffman tables: the tables of
     :func:`_jpeg_plan` (their Huffman words are not read), the header bytes before the DHT segment
     followed by those behind it, and the length of the first part."""
     from . import jpeg_format as jf
-    key = (device, H, W, quality, sampling, restart_mcus)
+    key = (device, H, W, quality, sampling, restart_mcus, layout)
     plan = _JPEG_OPT_PLANS.get(key)
     if plan is None:
-        pre, suf = jf.header_parts(H, W, quality, sampling, restart_mcus)
+        pre, suf = jf.header_parts(H, W, quality, sampling, restart_mcus, layout)
         if len(_JPEG_OPT_PLANS) >= 64:
             _JPEG_OPT_PLANS.clear()
-        plan = _JPEG_OPT_PLANS[key] = (_jpeg_plan(device, H, W, quality, sampling, restart_mcus)[0],
+        plan = _JPEG_OPT_PLANS[key] = (_jpeg_plan(device, H, W, quality, sampling, restart_mcus, layout)[0],
                                        torch.frombuffer(bytearray(pre + suf), dtype=torch.uint8).to(device), len(pre))
     return plan
 
 
 def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: int = 4,
-                return_decoded: bool = False, entropy: str = "interval", huffman: str = "standard"):
+                return_decoded: bool = False, entropy: str = "interval", huffman: str = "standard",
+                transform: str = "matrix"):
     """Baseline JPEG (JFIF) of uint8 ``[B, H, W, 3]`` / ``[H, W, 3]`` images (a tensor, or a
     ``DeviceImage``): one complete JPEG byte string per image, bit for bit what
     ``ops.reference.jpeg_encode`` writes (the contract: ops/csrc/jpeg.hip).  ``sampling`` "420" |
@@ -883,6 +885,15 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
     flow below does not change (every image's header length rides with the image offsets).  Any
     value but ``"standard"`` / ``"optimized"`` is a ``ValueError``.
 
+    ``transform="libjpeg"``: libjpeg's forward transform (edge rules, chroma mean, ISLOW DCT, dummy
+    blocks) and header layout in place of the matrix DCT (the libjpeg forward contract:
+    ops/csrc/jpeg.hip).  With ``entropy="block"`` and ``restart_mcus=0`` the bytes are the file
+    PIL's ``Image.save(format="JPEG", quality=quality)`` writes for the same pixels
+    (``huffman="optimized"``: with ``optimize=True``); with restart markers they are
+    ``ops.reference.jpeg_encode(..., transform="libjpeg")``'s.  It works with both coders, both
+    Huffman modes and ``return_decoded``.  Any value but ``"matrix"`` / ``"libjpeg"`` is a
+    ``ValueError``.
+
     ``return_decoded``: ``(bytes per image, decoded)`` instead, ``decoded`` the uint8
     ``[B, H, W, 3]`` pixels a libjpeg decoder (PIL) gives for those bytes, bit for bit
     ``ops.reference.jpeg_decoded`` (the decode contract: ops/csrc/jpeg.hip): a tensor on the
@@ -898,19 +909,21 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
         raise ValueError(f"jpeg_encode: entropy must be one of {JPEG_ENTROPY_CODERS}, not {entropy!r}")
     if huffman not in JPEG_HUFFMAN_MODES:
         raise ValueError(f"jpeg_encode: huffman must be one of {JPEG_HUFFMAN_MODES}, not {huffman!r}")
+    if transform not in JPEG_TRANSFORMS:
+        raise ValueError(f"jpeg_encode: transform must be one of {JPEG_TRANSFORMS}, not {transform!r}")
     t = getattr(images, "tensor", images)
     if not isinstance(t, torch.Tensor):
-        outs = ref.jpeg_encode(images, quality, sampling, restart_mcus, huffman=huffman)
-        return (outs, ref.jpeg_decoded(images, quality, sampling)) if return_decoded else outs
+        outs = ref.jpeg_encode(images, quality, sampling, restart_mcus, huffman=huffman, transform=transform)
+        return (outs, ref.jpeg_decoded(images, quality, sampling, transform)) if return_decoded else outs
     if t.dim() == 3:
         t = t[None]
     if t.dim() != 4 or t.shape[-1] != 3 or t.dtype != torch.uint8 or t.numel() == 0:
         raise ValueError("jpeg_encode: uint8 [B, H, W, 3] or [H, W, 3] expected")
     if not _use_hip(t):
-        outs = ref.jpeg_encode(t, quality, sampling, restart_mcus, huffman=huffman)
+        outs = ref.jpeg_encode(t, quality, sampling, restart_mcus, huffman=huffman, transform=transform)
         if not return_decoded:
             return outs
-        return outs, torch.from_numpy(ref.jpeg_decoded(t, quality, sampling)).to(t.device)
+        return outs, torch.from_numpy(ref.jpeg_decoded(t, quality, sampling, transform)).to(t.device)
     from . import jpeg_format as jf
     quality, restart_mcus = int(quality), int(restart_mcus)
     if entropy == "interval" and restart_mcus < 1:
@@ -920,18 +933,22 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
     B, H, W, _ = t.shape
     _, nb, mx, my = jf.geometry(H, W, sampling)
     optimized = huffman == "optimized"
+    lj = int(transform == "libjpeg")
+    layout = jf.transform_layout(transform)
     opt, nopt, sfx = (), 0, ""
     if optimized:
         # the image's tables and header are built on the device: counts | code words, headers
         jf.check_count_range(mx * my * nb)
         if B > 65535:
             raise ValueError("jpeg_encode: at most 65535 images per call with optimised Huffman tables")
-        tables, header, split = _jpeg_opt_plan(t.device, H, W, quality, sampling, restart_mcus)
+        tables, header, split = _jpeg_opt_plan(t.device, H, W, quality, sampling, restart_mcus, layout)
         hopt = torch.empty(2 * B * 544, device=t.device, dtype=torch.int32)
-        hdrs = torch.empty(B * (header.numel() + 4 + 4 * (17 + 256)), device=t.device, dtype=torch.uint8)
+        # room for every image's DHT: one segment header, or four in the PIL layout
+        dht_cap = 4 + (jf.DHT_EXTRA_PIL if lj else 0) + 4 * (17 + 256)
+        hdrs = torch.empty(B * (header.numel() + dht_cap), device=t.device, dtype=torch.uint8)
         opt, nopt, sfx = (hopt, hdrs, split), B, "_opt"
     else:
-        tables, header = _jpeg_plan(t.device, H, W, quality, sampling, restart_mcus)
+        tables, header = _jpeg_plan(t.device, H, W, quality, sampling, restart_mcus, layout)
     t = t.contiguous()
     per = min(restart_mcus, mx * my) if restart_mcus else mx * my          # MCUs per interval
     nint = (mx * my + per - 1) // per
@@ -946,7 +963,7 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
         blk = torch.empty(B * mx * my * nb + B * nint, device=t.device, dtype=torch.int32)
         scratch = torch.empty(B * nint * stride, device=t.device, dtype=torch.int32)
         getattr(ext(), "jpeg_count_blocks" + sfx)(t, tables, header, coef, work, blk, scratch, stride, s420,
-                                                  restart_mcus, *opt)
+                                                  restart_mcus, lj, *opt)
         # device-to-host copy 1: the image offsets + the error word (+ the header lengths)
         base = work[: B + 2 + nopt].cpu().tolist()
         hdr_lens, base = base[B + 2:], base[: B + 2]
@@ -956,21 +973,21 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
             raise ValueError("jpeg: a Huffman code longer than 32 bits")
         out = torch.empty(base[-1] + 1, device=t.device, dtype=torch.uint8)
         getattr(ext(), "jpeg_write_blocks" + sfx)(t, tables, header, coef, work, blk, scratch, stride, s420,
-                                                  restart_mcus, out, base[-1], *opt)
+                                                  restart_mcus, lj, out, base[-1], *opt)
         host = out.cpu().numpy()                      # device-to-host copy 2: the payload + the error byte
         if host[-1]:
             raise RuntimeError("jpeg_encode: the block coder refused a payload index")
         mv = memoryview(host)
     else:
         work = torch.empty(2 * B * nint + B + 1 + nopt, device=t.device, dtype=torch.int32)
-        getattr(ext(), "jpeg_count" + sfx)(t, tables, header, coef, work, s420, restart_mcus, *opt)
+        getattr(ext(), "jpeg_count" + sfx)(t, tables, header, coef, work, s420, restart_mcus, lj, *opt)
         # device-to-host copy 1: the image offsets (+ the header lengths)
         base = work[: B + 1 + nopt].cpu().tolist()
         hdr_lens, base = base[B + 1:], base[: B + 1]
         if not all(hdr_lens):
             raise ValueError("jpeg: a Huffman code longer than 32 bits")
         out = torch.empty(base[-1], device=t.device, dtype=torch.uint8)
-        getattr(ext(), "jpeg_write" + sfx)(t, tables, header, coef, work, s420, restart_mcus, out, base[-1], *opt)
+        getattr(ext(), "jpeg_write" + sfx)(t, tables, header, coef, work, s420, restart_mcus, lj, out, base[-1], *opt)
         mv = memoryview(out.cpu().numpy())                # device-to-host copy 2: the payload
     outs = [bytes(mv[base[i]: base[i + 1]]) for i in range(B)]
     if not return_decoded:

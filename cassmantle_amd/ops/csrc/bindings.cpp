@@ -868,13 +868,15 @@ void decode_attention(const at::Tensor& q, const at::Tensor& k_cache, const at::
 // header, cap = header bytes + 4 + 4 * (17 + 256); header = the bytes before the DHT segment
 // (split of them) followed by those behind it; work has B more words behind base (and the error
 // word): every image's header length
+// lj: 1 = the libjpeg forward contract (jpeg.hip): its transform kernel; with opt the four DHT
+// segments of its header layout, so cap = header bytes + 4 * 4 + 4 * (17 + 256)
 struct JpegOptBufs {
   at::Tensor hopt, hdrs;
   int64_t split = 0;
 };
 
 JpegArgs jpeg_args(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                   at::Tensor& work, int64_t s420, int64_t restart, bool blocks = false,
+                   at::Tensor& work, int64_t s420, int64_t restart, int64_t lj, bool blocks = false,
                    const JpegOptBufs* opt = nullptr) {
   CHECK_DEV(images); CHECK_CONTIG(images); CHECK_DEV(tables); CHECK_CONTIG(tables); CHECK_DEV(header);
   CHECK_CONTIG(header); CHECK_DEV(coef); CHECK_CONTIG(coef); CHECK_DEV(work); CHECK_CONTIG(work);
@@ -887,7 +889,9 @@ JpegArgs jpeg_args(const at::Tensor& images, const at::Tensor& tables, const at:
   } else {
     TORCH_CHECK(restart >= 1 && restart < 65536, "jpeg: the HIP encoder needs 1 <= restart_mcus <= 65535");
   }
+  TORCH_CHECK(lj == 0 || lj == 1, "jpeg: lj 0 (matrix transform) or 1 (libjpeg forward contract)");
   JpegArgs a;
+  a.lj = (int)lj;
   a.img = images.data_ptr<uint8_t>();
   a.B = (int)images.size(0); a.H = (int)images.size(1); a.W = (int)images.size(2);
   TORCH_CHECK(a.H < 65536 && a.W < 65536, "jpeg: image sides must be below 65536");
@@ -899,7 +903,7 @@ JpegArgs jpeg_args(const at::Tensor& images, const at::Tensor& tables, const at:
   a.restart = (int)restart;
   a.nint = (int)((mcus + restart - 1) / restart);
   a.hdr_len = (int)header.numel();
-  const int hdr_cap = a.hdr_len + (opt ? 4 + 4 * (17 + 256) : 0);
+  const int hdr_cap = a.hdr_len + (opt ? (lj ? 4 * 4 : 4) + 4 * (17 + 256) : 0);
   // 32-bit payload offsets: bound by the coder's worst case (20 + 63 * 26 bits per block, 27 + 63 * 26
   // with optimised tables, every byte stuffed, one padding byte and one marker per interval)
   TORCH_CHECK((double)a.B * ((double)hdr_cap + (double)mcus * a.nb * (opt ? 417 : 416) + (double)a.nint * 3) < 2147483648.0,
@@ -922,7 +926,7 @@ JpegArgs jpeg_args(const at::Tensor& images, const at::Tensor& tables, const at:
     TORCH_CHECK(opt->split > 0 && opt->split < a.hdr_len, "jpeg: header = bytes before the DHT segment | bytes behind it");
     TORCH_CHECK(opt->hopt.scalar_type() == at::kInt && opt->hopt.numel() == 2LL * a.B * 544, "jpeg: hopt int32 [2 * B * 544]");
     TORCH_CHECK(opt->hdrs.scalar_type() == at::kByte && opt->hdrs.numel() == (long long)a.B * hdr_cap,
-                "jpeg: hdrs uint8 [B * (header bytes + 4 + 4 * (17 + 256))]");
+                "jpeg: hdrs uint8 [B * (header bytes + 4 (lj: 16) + 4 * (17 + 256))]");
     a.freq = reinterpret_cast<uint32_t*>(opt->hopt.data_ptr<int>());
     a.ihuff = a.freq + (long long)a.B * 544;
     a.hdrs = opt->hdrs.data_ptr<uint8_t>();
@@ -960,16 +964,16 @@ JpegBlkArgs jpeg_blk_args(const JpegArgs& a, at::Tensor& work, at::Tensor& blk, 
 
 void jpeg_count_blocks(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
                        at::Tensor& work, at::Tensor& blk, at::Tensor& scratch, int64_t stride, int64_t s420,
-                       int64_t restart) {
-  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, true);
+                       int64_t restart, int64_t lj) {
+  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, lj, true);
   launch_jpeg_count_blocks(a, jpeg_blk_args(a, work, blk, scratch, stride), cur_stream());
 }
 
 // out uint8 [total + 1]: the payload and, behind it, the write pass's error byte
 void jpeg_write_blocks(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
                        at::Tensor& work, at::Tensor& blk, at::Tensor& scratch, int64_t stride, int64_t s420,
-                       int64_t restart, at::Tensor& out, int64_t total) {
-  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, true);
+                       int64_t restart, int64_t lj, at::Tensor& out, int64_t total) {
+  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, lj, true);
   JpegBlkArgs k = jpeg_blk_args(a, work, blk, scratch, stride);
   CHECK_DEV(out); CHECK_CONTIG(out);
   TORCH_CHECK(out.scalar_type() == at::kByte && total > 0 && total < 2147483647LL && out.numel() == total + 1,
@@ -980,13 +984,13 @@ void jpeg_write_blocks(const at::Tensor& images, const at::Tensor& tables, const
 }
 
 void jpeg_count(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                at::Tensor& work, int64_t s420, int64_t restart) {
-  launch_jpeg_count(jpeg_args(images, tables, header, coef, work, s420, restart), cur_stream());
+                at::Tensor& work, int64_t s420, int64_t restart, int64_t lj) {
+  launch_jpeg_count(jpeg_args(images, tables, header, coef, work, s420, restart, lj), cur_stream());
 }
 
 void jpeg_write(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                at::Tensor& work, int64_t s420, int64_t restart, at::Tensor& out, int64_t total) {
-  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart);
+                at::Tensor& work, int64_t s420, int64_t restart, int64_t lj, at::Tensor& out, int64_t total) {
+  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, lj);
   CHECK_DEV(out); CHECK_CONTIG(out);
   // total = base[B] as read back by the caller: every store of the write pass lands below it
   TORCH_CHECK(out.scalar_type() == at::kByte && total > 0 && out.numel() == total, "jpeg: out uint8 [base[B]]");
@@ -997,18 +1001,18 @@ void jpeg_write(const at::Tensor& images, const at::Tensor& tables, const at::Te
 // The same four calls with optimised Huffman tables (JpegOptBufs above).
 void jpeg_count_blocks_opt(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
                            at::Tensor& work, at::Tensor& blk, at::Tensor& scratch, int64_t stride, int64_t s420,
-                           int64_t restart, at::Tensor& hopt, at::Tensor& hdrs, int64_t split) {
+                           int64_t restart, int64_t lj, at::Tensor& hopt, at::Tensor& hdrs, int64_t split) {
   const JpegOptBufs opt{hopt, hdrs, split};
-  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, true, &opt);
+  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, lj, true, &opt);
   launch_jpeg_count_blocks(a, jpeg_blk_args(a, work, blk, scratch, stride), cur_stream());
 }
 
 void jpeg_write_blocks_opt(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
                            at::Tensor& work, at::Tensor& blk, at::Tensor& scratch, int64_t stride, int64_t s420,
-                           int64_t restart, at::Tensor& out, int64_t total, at::Tensor& hopt, at::Tensor& hdrs,
-                           int64_t split) {
+                           int64_t restart, int64_t lj, at::Tensor& out, int64_t total, at::Tensor& hopt,
+                           at::Tensor& hdrs, int64_t split) {
   const JpegOptBufs opt{hopt, hdrs, split};
-  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, true, &opt);
+  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, lj, true, &opt);
   JpegBlkArgs k = jpeg_blk_args(a, work, blk, scratch, stride);
   CHECK_DEV(out); CHECK_CONTIG(out);
   TORCH_CHECK(out.scalar_type() == at::kByte && total > 0 && total < 2147483647LL && out.numel() == total + 1,
@@ -1019,16 +1023,17 @@ void jpeg_write_blocks_opt(const at::Tensor& images, const at::Tensor& tables, c
 }
 
 void jpeg_count_opt(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                    at::Tensor& work, int64_t s420, int64_t restart, at::Tensor& hopt, at::Tensor& hdrs, int64_t split) {
+                    at::Tensor& work, int64_t s420, int64_t restart, int64_t lj, at::Tensor& hopt, at::Tensor& hdrs,
+                    int64_t split) {
   const JpegOptBufs opt{hopt, hdrs, split};
-  launch_jpeg_count(jpeg_args(images, tables, header, coef, work, s420, restart, false, &opt), cur_stream());
+  launch_jpeg_count(jpeg_args(images, tables, header, coef, work, s420, restart, lj, false, &opt), cur_stream());
 }
 
 void jpeg_write_opt(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                    at::Tensor& work, int64_t s420, int64_t restart, at::Tensor& out, int64_t total, at::Tensor& hopt,
-                    at::Tensor& hdrs, int64_t split) {
+                    at::Tensor& work, int64_t s420, int64_t restart, int64_t lj, at::Tensor& out, int64_t total,
+                    at::Tensor& hopt, at::Tensor& hdrs, int64_t split) {
   const JpegOptBufs opt{hopt, hdrs, split};
-  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, false, &opt);
+  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, lj, false, &opt);
   CHECK_DEV(out); CHECK_CONTIG(out);
   TORCH_CHECK(out.scalar_type() == at::kByte && total > 0 && out.numel() == total, "jpeg: out uint8 [base[B]]");
   a.out = out.data_ptr<uint8_t>();

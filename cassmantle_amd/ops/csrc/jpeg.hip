@@ -256,8 +256,55 @@
 // (blockIdx.y = image, blockIdx.x tiles the image's intervals / blocks): a workgroup holds one
 // image's table in LDS as before.  One launch per pass still, and at most 65535 images per call.
 // The host flow is unchanged: no copy or synchronisation is added.
+//
+// LIBJPEG FORWARD CONTRACT (transform = "libjpeg"; jpeg_format.coefficients_libjpeg is its numpy
+// model, jpeg_fdct_lj.h the arithmetic): the coefficients, and with the header layout below and no
+// restart markers the whole file, that libjpeg (PIL's Image.save(format="JPEG", quality=q)) writes
+// for the same pixels.  It replaces the geometry's edge rule, the chroma mean and the DCT of the
+// byte contract; colour, level shift, quantisation formula, zig-zag order and entropy coding are
+// the byte contract's.  Integer arithmetic in 32-bit words (the model asserts the width).
+//
+//   Edges, 4:4:4.  Every plane is replicated (last column, last row) up to whole 8x8 blocks.
+//   Edges and chroma, 4:2:0.  ch = ceil(H/2), cw = ceil(W/2); the chroma plane has cbh = ceil(ch/8)
+//   x cbw = ceil(cw/8) blocks (= the MCU grid).  Full-resolution Cb / Cr are replicated to 2 ch
+//   rows (an even row count, no further) and to 16 cbw columns; then
+//     c[r][x] = (p[2r][2x] + p[2r][2x+1] + p[2r+1][2x] + p[2r+1][2x+1] + bias) >> 2,
+//     bias = 1 for even x, 2 for odd x;
+//   then the downsampled rows are replicated from ch to 8 cbh.  In source coordinates: chroma
+//   sample (r, x) reads rows y0 = 2 min(r, ch-1) and min(y0+1, H-1), columns min(2x, W-1) and
+//   min(2x+1, W-1).  (Replicating the image rows to 16 and averaging afterwards differs when H is
+//   even and no multiple of 16.)  Luma is replicated to 8 ceil(H/8) x 8 ceil(W/8).
+//
+//   DCT (jfdctint, ISLOW, CONST_BITS 13, PASS1_BITS 2): the 8 rows first, then the 8 columns.
+//   One 8-point pass on d0..d7, D(x, n) = (x + 2^(n-1)) >> n:
+//     t0..t3 = d0+d7  d1+d6  d2+d5  d3+d4;   t7..t4 = d0-d7  d1-d6  d2-d5  d3-d4
+//     t10 = t0+t3;  t13 = t0-t3;  t11 = t1+t2;  t12 = t1-t2
+//     rows:     o0 = (t10+t11) << 2;  o4 = (t10-t11) << 2;  s = 11
+//     columns:  o0 = D(t10+t11, 2);   o4 = D(t10-t11, 2);   s = 15
+//     z1 = (t12+t13) * 4433;  o2 = D(z1 + t13 * 6270, s);  o6 = D(z1 - t12 * 15137, s)
+//     z1 = t4+t7;  z2 = t5+t6;  z3 = t4+t6;  z4 = t5+t7;  z5 = (z3+z4) * 9633
+//     t4 *= 2446;  t5 *= 16819;  t6 *= 25172;  t7 *= 12299
+//     z1 *= -7373;  z2 *= -20995;  z3 = z3 * -16069 + z5;  z4 = z4 * -3196 + z5
+//     o7 = D(t4+z1+z3, s);  o5 = D(t5+z2+z4, s);  o3 = D(t6+z2+z3, s);  o1 = D(t7+z1+z4, s)
+//   The result is 8 x the DCT coefficient, quantised as in the byte contract.  The AC clamp
+//   +-1023 stays as a guard and never fires: the largest |AC| of 8-bit samples is 1020 at q 100.
+//
+//   Dummy blocks (4:2:0).  A luma block of an MCU whose block row is >= ceil(H/8) or whose block
+//   column is >= ceil(W/8) is not transformed: all its AC values are 0 and its DC is the quantised
+//   DC of the previous block of the same MCU in the order Y00 Y01 Y10 Y11, itself a dummy or not
+//   (at 1x1, Y01 Y10 Y11 all carry Y00's DC).  Chroma blocks are always real.
+//
+//   Header (jpeg_format.header(layout="pil")): SOI, APP0, a DQT segment per quantisation table
+//   (0, 1), SOF0, a DHT segment per Huffman table (DC0, AC0, DC1, AC1), DRI only with a restart
+//   interval, SOS; the same with optimised tables, whose four segments the build kernel writes.
+//
+// Kernel: jpeg_transform_lj_kernel, the shape of jpeg_transform_kernel (one wave per MCU, samples
+// in LDS, a lane owns a row and then a column of a block) with the butterfly above in place of
+// DCTM (12 multiplies per 8 points instead of 64) and, after quantisation, the wave-uniform
+// dummy-block pass.  Everything behind the coefficient buffer is unchanged.
 #include "common.h"
 #include "kernels.h"
+#include "jpeg_fdct_lj.h"
 #include "jpeg_entropy_dec.h"
 #include "jpeg_entropy_sync.h"
 #include "jpeg_entropy_blk.h"
@@ -384,6 +431,114 @@ __global__ __launch_bounds__(64 * TR_WAVES) void jpeg_transform_kernel(JpegArgs 
     for (int i = lane; i < NB * 32; i += 64)
       dst[i] = ((uint32_t)s[2 * i] & 0xffffu) | ((uint32_t)s[2 * i + 1] << 16);
   }
+}
+
+// ---------------------------------------------------------------------------------- libjpeg transform
+// The LIBJPEG FORWARD CONTRACT in the shape of jpeg_transform_kernel.  Row r of block b lies at
+// LDS word lj_row(b, r): the rows of a block are rotated by the block's index, so that the column
+// pass, where the lanes of a 32-lane half hold the same row of four blocks, reads four different
+// banks (ds_read_b32: bank = word mod 32) instead of one four times; a row stays 8 consecutive,
+// 32-byte aligned words for the row pass.
+CM_DEVICE int lj_row(int b, int r) { return b * 64 + (((r + b) & 7) << 3); }
+
+template <bool S420>
+__global__ __launch_bounds__(64 * TR_WAVES) void jpeg_transform_lj_kernel(JpegArgs a) {
+  constexpr int NB = S420 ? 6 : 3;
+  __shared__ int sm[TR_WAVES][NB * 64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int mcus = a.mx * a.my;
+  const long long g = (long long)blockIdx.x * TR_WAVES + wave;
+  const bool valid = g < (long long)a.B * mcus;
+  int* s = sm[wave];
+  int mby = 0, mbx = 0;
+  if (valid) {
+    const int b = (int)(g / mcus), m = (int)(g % mcus);
+    mby = m / a.mx;
+    mbx = m % a.mx;
+    const uint8_t* img = a.img + (long long)b * a.H * a.W * 3;
+    if (S420) {
+      const int qy = lane >> 3, qx = lane & 7;
+      const int y0 = mby * 16, x0 = mbx * 16;
+      int cy[2];
+      jpeg_lj_chroma_rows(mby * 8 + qy, a.H, cy[0], cy[1]);
+      int cb = 0, cr = 0;
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        const int yy = 2 * qy + (d >> 1), xx = 2 * qx + (d & 1);
+        const int y = jpeg_lj_src(y0 + yy, a.H), x = jpeg_lj_src(x0 + xx, a.W);
+        JpegLjYcc c = jpeg_lj_ycc(img + ((long long)y * a.W + x) * 3);
+        s[lj_row((yy >> 3) * 2 + (xx >> 3), yy & 7) + (xx & 7)] = c.y - 128;
+        // below the last real chroma row the mean is that row's again, not the luma rows' own
+        if (cy[d >> 1] != y) c = jpeg_lj_ycc(img + ((long long)cy[d >> 1] * a.W + x) * 3);
+        cb += c.cb;
+        cr += c.cr;
+      }
+      s[lj_row(4, qy) + qx] = jpeg_lj_chroma_mean(cb, qx) - 128;
+      s[lj_row(5, qy) + qx] = jpeg_lj_chroma_mean(cr, qx) - 128;
+    } else {
+      const int r = lane >> 3, c8 = lane & 7;
+      const int y = jpeg_lj_src(mby * 8 + r, a.H), x = jpeg_lj_src(mbx * 8 + c8, a.W);
+      const JpegLjYcc c = jpeg_lj_ycc(img + ((long long)y * a.W + x) * 3);
+      s[lj_row(0, r) + c8] = c.y - 128;
+      s[lj_row(1, r) + c8] = c.cb - 128;
+      s[lj_row(2, r) + c8] = c.cr - 128;
+    }
+  }
+  __syncthreads();
+  const bool worker = valid && lane < NB * 8;
+  const int blk = lane >> 3, col = lane & 7;
+  if (worker) {                       // rows
+    int* row = s + lj_row(blk, col);
+    int x[8];
+#pragma unroll
+    for (int n = 0; n < 8; ++n) x[n] = row[n];
+    jpeg_lj_fdct8<true>(x);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) row[k] = x[k];
+  }
+  __syncthreads();
+  int v[8];
+  if (worker) {                       // columns + quantisation
+#pragma unroll
+    for (int n = 0; n < 8; ++n) v[n] = s[lj_row(blk, n) + col];
+    jpeg_lj_fdct8<false>(v);
+    const int* q = a.qtab + (blk < NB - 2 ? 0 : 64);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = jpeg_lj_quant(v[k], q[k * 8 + col], k * 8 + col != 0);
+  }
+  __syncthreads();
+  if (worker) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s[blk * 64 + ZPOS[k * 8 + col]] = v[k];
+  }
+  __syncthreads();
+  if (S420 && valid) {                // dummy luma blocks: the tests are the same in every lane of the wave
+    int dc = s[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) {
+      if (jpeg_lj_dummy(k, mby, mbx, a.H, a.W)) s[k * 64 + lane] = lane == 0 ? dc : 0;
+      else dc = s[k * 64];
+    }
+  }
+  __syncthreads();
+  if (valid) {
+    uint32_t* dst = reinterpret_cast<uint32_t*>(a.coef + g * (NB * 64));
+    for (int i = lane; i < NB * 32; i += 64)
+      dst[i] = ((uint32_t)s[2 * i] & 0xffffu) | ((uint32_t)s[2 * i + 1] << 16);
+  }
+}
+
+// the forward transform a.lj selects, one wave per MCU
+static void launch_jpeg_transform(const JpegArgs& a, hipStream_t s) {
+  const long long mcus = (long long)a.B * a.mx * a.my;
+  const unsigned tg = (unsigned)((mcus + TR_WAVES - 1) / TR_WAVES);
+  if (a.lj) {
+    if (a.nb == 6) hipLaunchKernelGGL(jpeg_transform_lj_kernel<true>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
+    else hipLaunchKernelGGL(jpeg_transform_lj_kernel<false>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
+    return;
+  }
+  if (a.nb == 6) hipLaunchKernelGGL(jpeg_transform_kernel<true>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
+  else hipLaunchKernelGGL(jpeg_transform_kernel<false>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------------- entropy coder
@@ -603,7 +758,7 @@ __global__ __launch_bounds__(256) void jpeg_huff_build_kernel(JpegArgs a) {
   uint8_t* dst = a.hdrs + (long long)b * a.hdr_cap;
   for (int i = tid; i < pre; i += 256) dst[i] = a.header[i];
   const uint32_t room = (uint32_t)max(a.hdr_cap - pre - suf, 0);
-  const uint32_t dht = jpeg_huff_dht(work, dst + pre, room, tid, 256);
+  const uint32_t dht = jpeg_huff_dht(work, dst + pre, room, tid, 256, a.lj != 0);
   const bool ok = dht <= room && (work[0].bad | work[1].bad | work[2].bad | work[3].bad) == 0u;
   if (ok)
     for (int i = tid; i < suf; i += 256) dst[pre + dht + i] = a.header[pre + i];
@@ -1179,10 +1334,7 @@ static int blk_threads(long long items) {
 
 void launch_jpeg_count_blocks(const JpegArgs& a, const JpegBlkArgs& k, hipStream_t s) {
   launch_zero(k.err, 4, s);
-  const long long mcus = (long long)a.B * a.mx * a.my;
-  const unsigned tg = (unsigned)((mcus + TR_WAVES - 1) / TR_WAVES);
-  if (a.nb == 6) hipLaunchKernelGGL(jpeg_transform_kernel<true>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
-  else hipLaunchKernelGGL(jpeg_transform_kernel<false>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
+  launch_jpeg_transform(a, s);
   if (a.ihuff != nullptr) launch_jpeg_huff_opt(a, s);
   const dim3 bg = item_grid(a, (long long)a.mx * a.my * a.nb, BLK_LANES);
   const unsigned ig = (unsigned)((long long)a.B * a.nint);
@@ -1206,10 +1358,7 @@ void launch_jpeg_write_blocks(const JpegArgs& a, const JpegBlkArgs& k, hipStream
 }
 
 void launch_jpeg_count(const JpegArgs& a, hipStream_t s) {
-  const long long mcus = (long long)a.B * a.mx * a.my;
-  const unsigned tg = (unsigned)((mcus + TR_WAVES - 1) / TR_WAVES);
-  if (a.nb == 6) hipLaunchKernelGGL(jpeg_transform_kernel<true>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
-  else hipLaunchKernelGGL(jpeg_transform_kernel<false>, dim3(tg), dim3(64 * TR_WAVES), 0, s, a);
+  launch_jpeg_transform(a, s);
   if (a.ihuff != nullptr) launch_jpeg_huff_opt(a, s);
   hipLaunchKernelGGL(jpeg_entropy_kernel<false>, item_grid(a, a.nint, 64), dim3(64), 0, s, a);
   hipLaunchKernelGGL(jpeg_scan_image_kernel, dim3(a.B), dim3(256), 0, s, a);

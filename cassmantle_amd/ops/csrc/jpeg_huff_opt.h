@@ -170,9 +170,27 @@ JPEG_HUFF_FN void jpeg_huff_assign(JpegHuffWork& w, uint32_t* words, int nslots,
 // The DHT segment of an image's four tables t[0 .. 3] = DC luma, DC chroma, AC luma, AC chroma,
 // written in the order DC luma, AC luma, DC chroma, AC chroma at dst[0 .. cap): thread tid of
 // nthreads stores the bytes tid, tid + nthreads, ...  Returns the segment's length, the same in
-// every thread; a byte at or past cap is not stored.
-JPEG_HUFF_FN uint32_t jpeg_huff_dht(const JpegHuffWork* t, uint8_t* dst, uint32_t cap, int tid, int nthreads) {
+// every thread; a byte at or past cap is not stored.  per_table: a segment per table, each with
+// its own marker and length (the layout libjpeg writes), in the same order.
+JPEG_HUFF_FN uint32_t jpeg_huff_dht(const JpegHuffWork* t, uint8_t* dst, uint32_t cap, int tid, int nthreads,
+                                    bool per_table = false) {
   // segment slot s = 0..3 holds table ((s & 1) << 1) | (s >> 1) under the id Tc = s & 1, Th = s >> 1
+  if (per_table) {
+    uint32_t at = 0;
+    for (int s = 0; s < 4; ++s) {
+      const JpegHuffWork& w = t[((s & 1) << 1) | (s >> 1)];
+      const uint32_t n = 4u + 17u + w.nvals;
+      for (uint32_t i = (uint32_t)tid; i < n; i += (uint32_t)nthreads) {
+        uint32_t v;
+        if (i < 4u) v = i == 0u ? 0xffu : (i == 1u ? 0xc4u : (i == 2u ? ((n - 2u) >> 8) : ((n - 2u) & 0xffu)));
+        else if (i == 4u) v = (uint32_t)(((s & 1) << 4) | (s >> 1));
+        else v = i < 21u ? (uint32_t)w.bits[i - 4u] : w.vals[i - 21u];
+        if (at + i < cap) dst[at + i] = (uint8_t)v;
+      }
+      at += n;
+    }
+    return at;
+  }
   uint32_t len = 4;
   for (int s = 0; s < 4; ++s) len += 17u + t[s].nvals;
   for (uint32_t i = (uint32_t)tid; i < len; i += (uint32_t)nthreads) {

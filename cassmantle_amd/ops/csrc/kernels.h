@@ -226,6 +226,9 @@ struct JpegArgs {
   uint32_t* base = nullptr;          // [B + 1] byte offset of every image in the payload
   const uint8_t* header = nullptr;   // SOI .. SOS, the same for every image of the batch
   int hdr_len = 0;
+  // 1: the libjpeg forward contract (jpeg_fdct_lj.h): its transform kernel, and with optimised
+  // tables a DHT segment per table in every image's header
+  int lj = 0;
   uint8_t* out = nullptr;            // payload (launch_jpeg_write)
   // launch_jpeg_reconstruct (decode contract in jpeg.hip's header comment)
   uint8_t* planes = nullptr;         // scratch: Y [B][yh][yw], Cb, Cr [B][8 my][8 mx]; yh x yw = 16 my x 16 mx (4:2:0) or 8 my x 8 mx

@@ -152,28 +152,49 @@ def _seg(marker: int, payload: bytes) -> bytes:
     return struct.pack(">BBH", 0xFF, marker, len(payload) + 2) + payload
 
 
-def header(H: int, W: int, quality: int, sampling: str, restart_mcus: int, tables=None) -> bytes:
+TRANSFORMS = ("matrix", "libjpeg")
+HEADER_LAYOUTS = ("compact", "pil")    # one DQT and one DHT segment | a segment per table, as libjpeg writes them
+DHT_EXTRA_PIL = 3 * 4                  # the three more segment headers of the PIL layout's DHT
+
+
+def transform_layout(transform: str) -> str:
+    """The header layout that goes with a forward transform: ``"libjpeg"`` writes PIL's file."""
+    if transform not in TRANSFORMS:
+        raise ValueError(f"jpeg: transform must be one of {TRANSFORMS}, not {transform!r}")
+    return "pil" if transform == "libjpeg" else "compact"
+
+
+def header(H: int, W: int, quality: int, sampling: str, restart_mcus: int, tables=None,
+           layout: str = "compact") -> bytes:
     """SOI / APP0 / DQT / SOF0 / DHT / DRI / SOS for one image (the entropy-coded data and EOI
     follow).  ``tables``: four ``(bits, vals)`` (DC luma, DC chroma, AC luma, AC chroma) written into
     the one DHT segment in place of the standard ones, in the same order (DC luma, AC luma, DC
-    chroma, AC chroma)."""
-    pre, suf = header_parts(H, W, quality, sampling, restart_mcus)
-    return pre + dht_segment(tables) + suf
+    chroma, AC chroma).  ``layout="pil"``: the segments libjpeg (PIL) writes: a DQT segment per
+    quantisation table and a DHT segment per Huffman table, in that same order."""
+    pre, suf = header_parts(H, W, quality, sampling, restart_mcus, layout)
+    return pre + dht_segment(tables, layout) + suf
 
 
-def dht_segment(tables=None) -> bytes:
-    """The DHT segment of four ``(bits, vals)`` (default: the standard tables)."""
+def dht_segment(tables=None, layout: str = "compact") -> bytes:
+    """The DHT segment of four ``(bits, vals)`` (default: the standard tables); with
+    ``layout="pil"`` the four segments, one per table."""
+    if layout not in HEADER_LAYOUTS:
+        raise ValueError(f"jpeg: layout must be one of {HEADER_LAYOUTS}, not {layout!r}")
     t = STANDARD_TABLES if tables is None else _frozen_tables(tables)
-    dht = b""
-    for tc_th, (bits, vals) in ((0x00, t[0]), (0x10, t[2]), (0x01, t[1]), (0x11, t[3])):
-        dht += bytes([tc_th]) + bytes(bits) + bytes(vals)
-    return _seg(0xC4, dht)
+    parts = [bytes([tc_th]) + bytes(bits) + bytes(vals)
+             for tc_th, (bits, vals) in ((0x00, t[0]), (0x10, t[2]), (0x01, t[1]), (0x11, t[3]))]
+    if layout == "pil":
+        return b"".join(_seg(0xC4, p) for p in parts)
+    return _seg(0xC4, b"".join(parts))
 
 
 @lru_cache(maxsize=64)
-def header_parts(H: int, W: int, quality: int, sampling: str, restart_mcus: int) -> Tuple[bytes, bytes]:
-    """(the header bytes before the DHT segment, those after it): the same for every image of a
+def header_parts(H: int, W: int, quality: int, sampling: str, restart_mcus: int,
+                 layout: str = "compact") -> Tuple[bytes, bytes]:
+    """(the header bytes before the DHT segment(s), those after): the same for every image of a
     geometry, whatever its Huffman tables."""
+    if layout not in HEADER_LAYOUTS:
+        raise ValueError(f"jpeg: layout must be one of {HEADER_LAYOUTS}, not {layout!r}")
     if not (0 < H < 65536 and 0 < W < 65536):
         raise ValueError("jpeg: image sides must be in 1..65535")
     if not 0 <= restart_mcus < 65536:
@@ -182,7 +203,10 @@ def header_parts(H: int, W: int, quality: int, sampling: str, restart_mcus: int)
     lq, cq = quant_tables(quality)
     out = b"\xff\xd8"
     out += _seg(0xE0, b"JFIF\x00\x01\x01\x00" + struct.pack(">HHBB", 1, 1, 0, 0))
-    out += _seg(0xDB, bytes([0]) + bytes(lq[i] for i in ZIGZAG) + bytes([1]) + bytes(cq[i] for i in ZIGZAG))
+    if layout == "pil":
+        out += _seg(0xDB, bytes([0]) + bytes(lq[i] for i in ZIGZAG)) + _seg(0xDB, bytes([1]) + bytes(cq[i] for i in ZIGZAG))
+    else:
+        out += _seg(0xDB, bytes([0]) + bytes(lq[i] for i in ZIGZAG) + bytes([1]) + bytes(cq[i] for i in ZIGZAG))
     hv = 0x22 if sampling == "420" else 0x11
     out += _seg(0xC0, struct.pack(">BHHB", 8, H, W, 3) + bytes([1, hv, 0, 2, 0x11, 1, 3, 0x11, 1]))
     suf = b""
@@ -197,8 +221,15 @@ def _div_floor_shift(x: np.ndarray, sh: int) -> np.ndarray:
     return (x + (1 << (sh - 1))) >> sh        # arithmetic shift: floor((x + half) / 2^sh)
 
 
-def coefficients(img: np.ndarray, quality: int, sampling: str) -> np.ndarray:
-    """uint8 [H, W, 3] -> int16 [mcus, blocks per MCU, 64] quantised zig-zag coefficients."""
+def coefficients(img: np.ndarray, quality: int, sampling: str, transform: str = "matrix",
+                 stats: dict = None) -> np.ndarray:
+    """uint8 [H, W, 3] -> int16 [mcus, blocks per MCU, 64] quantised zig-zag coefficients.
+    ``transform="libjpeg"``: libjpeg's forward path (:func:`coefficients_libjpeg`) in place of the
+    matrix DCT of the byte contract; ``stats`` is handed on to it."""
+    if transform not in TRANSFORMS:
+        raise ValueError(f"jpeg: transform must be one of {TRANSFORMS}, not {transform!r}")
+    if transform == "libjpeg":
+        return coefficients_libjpeg(img, quality, sampling, stats)
     H, W, _ = img.shape
     m, nb, mx, my = geometry(H, W, sampling)
     # edge replication up to a whole MCU
@@ -237,6 +268,141 @@ def coefficients(img: np.ndarray, quality: int, sampling: str) -> np.ndarray:
     v = np.sign(f) * ((np.abs(f) + (q >> 1)) // q)          # round half away from zero
     v = v.reshape(my * mx, nb, 64)
     v[..., 1:] = np.clip(v[..., 1:], -1023, 1023)           # baseline AC magnitude categories 1..10
+    return v[..., ZIGZAG].astype(np.int16)
+
+
+# ----------------------------------------------------------------------------- libjpeg forward contract
+# The coefficients libjpeg (PIL's encoder) computes: the LIBJPEG FORWARD CONTRACT section of
+# jpeg.hip's header comment; ops/csrc/jpeg_fdct_lj.h is the arithmetic the kernel and the host
+# program compile.
+FDCT_BITS = 13                         # libjpeg jfdctint CONST_BITS
+FDCT_PASS1 = 2                         # PASS1_BITS
+
+
+def _fdct_pass(d, first: bool, see):
+    """One 8-point pass of the jfdctint forward DCT on the arrays d[0..7] (``first``: the row
+    pass); ``see`` is handed every intermediate (the word-width check) and returns it."""
+    def D(x, n):
+        return see(x + (1 << (n - 1))) >> n
+    t0, t1, t2, t3 = d[0] + d[7], d[1] + d[6], d[2] + d[5], d[3] + d[4]
+    t7, t6, t5, t4 = d[0] - d[7], d[1] - d[6], d[2] - d[5], d[3] - d[4]
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    if first:
+        o0, o4 = see((t10 + t11) << FDCT_PASS1), see((t10 - t11) << FDCT_PASS1)
+        sh = FDCT_BITS - FDCT_PASS1
+    else:
+        o0, o4 = D(t10 + t11, FDCT_PASS1), D(t10 - t11, FDCT_PASS1)
+        sh = FDCT_BITS + FDCT_PASS1
+    z1 = see((t12 + t13) * 4433)
+    o2, o6 = D(z1 + see(t13 * 6270), sh), D(z1 - see(t12 * 15137), sh)
+    z1, z2, z3, z4 = t4 + t7, t5 + t6, t4 + t6, t5 + t7
+    z5 = see((z3 + z4) * 9633)
+    t4, t5, t6, t7 = see(t4 * 2446), see(t5 * 16819), see(t6 * 25172), see(t7 * 12299)
+    z1, z2 = see(z1 * -7373), see(z2 * -20995)
+    z3, z4 = see(see(z3 * -16069) + z5), see(see(z4 * -3196) + z5)
+    o7, o5 = D(see(see(t4 + z1) + z3), sh), D(see(see(t5 + z2) + z4), sh)
+    o3, o1 = D(see(see(t6 + z2) + z3), sh), D(see(see(t7 + z1) + z4), sh)
+    return [o0, o1, o2, o3, o4, o5, o6, o7]
+
+
+def fdct_libjpeg(blk: np.ndarray, see=lambda v: v) -> np.ndarray:
+    """Level-shifted samples [..., 8, 8] -> 8 x the DCT coefficients [..., 8, 8] (jfdctint: rows,
+    then columns)."""
+    blk = np.asarray(blk, dtype=np.int64)
+    t = np.stack(_fdct_pass([blk[..., n] for n in range(8)], True, see), axis=-1)
+    return np.stack(_fdct_pass([t[..., n, :] for n in range(8)], False, see), axis=-2)
+
+
+def quantise_libjpeg(f: np.ndarray, q: np.ndarray) -> np.ndarray:
+    """8 x coefficients [..., 8, 8] and quantisation values ``q`` (natural order, broadcast) ->
+    quantised values: round half away from zero, AC guarded at +-1023."""
+    q8 = np.asarray(q, dtype=np.int64) << 3
+    v = np.sign(f) * ((np.abs(f) + (q8 >> 1)) // q8)
+    flat = v.reshape(v.shape[:-2] + (64,))
+    flat[..., 1:] = np.clip(flat[..., 1:], -1023, 1023)
+    return flat
+
+
+def coefficients_libjpeg(img: np.ndarray, quality: int, sampling: str, stats: dict = None) -> np.ndarray:
+    """uint8 [H, W, 3] -> int16 [mcus, blocks per MCU, 64]: the quantised zig-zag coefficients of
+    the file ``Image.save(format="JPEG", quality=quality)`` writes for these pixels (libjpeg's
+    edge expansion, h2v2 downsampling, ISLOW forward DCT and dummy blocks).  ``stats`` receives
+    ``max_abs`` (the largest intermediate of the DCT: the kernel works in 32-bit words),
+    ``dummy_blocks``, ``dummy_chain`` (dummy blocks whose DC comes from another dummy block),
+    ``chroma_bottom_rows`` (downsampled chroma rows that are replicas while their two source rows
+    lie inside the 16-row MCU: the even-H rule), ``odd_row_pairs`` (chroma rows averaging a
+    replicated image row), ``bias1`` / ``bias2`` (chroma means whose result depends on the bias
+    being 1 / 2 and not the other), ``ac_clamped``."""
+    H, W, _ = img.shape
+    m, nb, mx, my = geometry(H, W, sampling)
+    p = img.astype(np.int64)
+    R, G, B = p[..., 0], p[..., 1], p[..., 2]
+    Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16
+    Cb = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16
+    Cr = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16
+    st = {"max_abs": 0, "dummy_blocks": 0, "dummy_chain": 0, "chroma_bottom_rows": 0, "odd_row_pairs": 0,
+          "bias1": 0, "bias2": 0, "ac_clamped": 0}
+
+    def see(v):
+        st["max_abs"] = max(st["max_abs"], int(np.abs(v).max()))
+        return v
+
+    def pad(c: np.ndarray, h: int, w: int) -> np.ndarray:      # replicate the last row / column
+        return c[np.minimum(np.arange(h), c.shape[0] - 1)][:, np.minimum(np.arange(w), c.shape[1] - 1)]
+
+    def blocks(c: np.ndarray) -> np.ndarray:       # [h, w] -> [h/8, w/8, 8, 8], level-shifted
+        h, w = c.shape
+        return (c - 128).reshape(h // 8, 8, w // 8, 8).transpose(0, 2, 1, 3)
+
+    bh, bw = (H + 7) // 8, (W + 7) // 8            # real luma blocks
+    if sampling == "420":
+        ch, cw = (H + 1) // 2, (W + 1) // 2
+        cbh, cbw = (ch + 7) // 8, (cw + 7) // 8
+
+        def sub(c: np.ndarray) -> np.ndarray:
+            c = pad(c, 2 * ch, 16 * cbw)
+            s4 = c[0::2, 0::2] + c[0::2, 1::2] + c[1::2, 0::2] + c[1::2, 1::2]
+            bias = np.where(np.arange(8 * cbw) & 1, 2, 1)
+            real = s4[:, :cw]
+            st["bias1"] += int(((real[:, 0::2] & 3) == 2).sum())       # +1 stays below, +2 carries
+            st["bias2"] += int(((real[:, 1::2] & 3) == 2).sum())
+            return pad((s4 + bias) >> 2, 8 * cbh, 8 * cbw)
+        Cb, Cr = sub(Cb), sub(Cr)
+        st["odd_row_pairs"] += H & 1
+        st["chroma_bottom_rows"] += 8 * cbh - ch if (H % 16) else 0
+        assert (cbh, cbw) == (my, mx)
+        Yp = pad(pad(Y, 8 * bh, 8 * bw), 16 * my, 16 * mx)          # dummy blocks are replaced below
+        yb = blocks(Yp).reshape(my, 2, mx, 2, 8, 8).transpose(0, 2, 1, 3, 4, 5).reshape(my, mx, 4, 8, 8)
+        blk = np.concatenate([yb, blocks(Cb)[:, :, None], blocks(Cr)[:, :, None]], axis=2)
+    else:
+        blk = np.stack([blocks(pad(c, 8 * bh, 8 * bw)) for c in (Y, Cb, Cr)], axis=2)
+    blk = blk.reshape(my * mx, nb, 8, 8)
+    f = fdct_libjpeg(blk, see)
+    if st["max_abs"] >= 1 << 31:
+        raise AssertionError("jpeg: a forward DCT intermediate does not fit 32 bits")
+    lq, cq = quant_tables(quality)
+    q = np.empty((nb, 8, 8), dtype=np.int64)
+    q[:nb - 2] = np.asarray(lq).reshape(8, 8)
+    q[nb - 2:] = np.asarray(cq).reshape(8, 8)
+    raw = np.sign(f) * ((np.abs(f) + (q << 2)) // (q << 3))
+    st["ac_clamped"] = int((np.abs(raw.reshape(-1, nb, 64)[..., 1:]) > 1023).sum())
+    v = quantise_libjpeg(f, q)
+    if sampling == "420":
+        # dummy luma blocks: no AC, the DC of the MCU's previous block (which may be a dummy itself)
+        v = v.reshape(my, mx, nb, 64)
+        for k in range(1, 4):
+            dy, dx = k >> 1, k & 1
+            dummy = ((2 * np.arange(my) + dy >= bh)[:, None] | (2 * np.arange(mx) + dx >= bw)[None, :])
+            prev_dummy = ((2 * np.arange(my) + ((k - 1) >> 1) >= bh)[:, None]
+                          | (2 * np.arange(mx) + ((k - 1) & 1) >= bw)[None, :])
+            st["dummy_blocks"] += int(dummy.sum())
+            st["dummy_chain"] += int((dummy & prev_dummy).sum())
+            fill = np.zeros_like(v[:, :, k])
+            fill[..., 0] = v[:, :, k - 1, 0]
+            v[:, :, k] = np.where(dummy[..., None], fill, v[:, :, k])
+        v = v.reshape(my * mx, nb, 64)
+    if stats is not None:
+        stats.update(st)
     return v[..., ZIGZAG].astype(np.int16)
 
 
@@ -460,33 +626,37 @@ def entropy_blocks(coef: np.ndarray, restart_mcus: int, stuff_chunk: int = BLK_S
 
 
 def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: int = 4,
-                return_stats: bool = False, huffman: str = "standard"):
+                return_stats: bool = False, huffman: str = "standard", transform: str = "matrix"):
     """Baseline JPEG of uint8 ``[B, H, W, 3]`` (or ``[H, W, 3]``) images: one byte string per
     image.  ``restart_mcus`` MCUs per restart interval (0: no DRI, one interval).  With
     ``return_stats`` also a dict per image: ``stuffed`` (0xFF bytes that needed a stuffed zero),
     ``zrl`` (ZRL symbols), ``max_dc_cat`` (largest DC difference category), ``intervals``.
     ``huffman="optimized"``: every image is coded with, and carries in its DHT, the tables
     :func:`optimal_table` builds from its own :func:`symbol_counts` (what libjpeg's ``optimize``
-    writes for those coefficients)."""
+    writes for those coefficients).  ``transform="libjpeg"``: libjpeg's forward transform and
+    header layout (the libjpeg forward contract): with ``restart_mcus=0`` the file PIL's
+    ``Image.save(format="JPEG", quality=quality)`` writes, byte for byte (``huffman="optimized"``:
+    with ``optimize=True``)."""
     if huffman not in HUFFMAN_MODES:
         raise ValueError(f"jpeg_encode: huffman must be one of {HUFFMAN_MODES}, not {huffman!r}")
+    layout = transform_layout(transform)
     arr = images.detach().cpu().numpy() if hasattr(images, "detach") else np.asarray(images)
     if arr.ndim == 3:
         arr = arr[None]
     if arr.ndim != 4 or arr.shape[-1] != 3 or arr.dtype != np.uint8:
         raise ValueError("jpeg_encode: uint8 [B, H, W, 3] or [H, W, 3] expected")
     _, H, W, _ = arr.shape
-    hdr = header(H, W, int(quality), sampling, int(restart_mcus))
+    hdr = header(H, W, int(quality), sampling, int(restart_mcus), None, layout)
     if huffman == "optimized":
         _, nb, mx, my = geometry(H, W, sampling)
         check_count_range(mx * my * nb)
     outs, stats = [], []
     for img in arr:
-        coef = coefficients(img, int(quality), sampling)
+        coef = coefficients(img, int(quality), sampling, transform)
         tables = None
         if huffman == "optimized":
             tables = optimal_tables(symbol_counts(coef, int(restart_mcus)))
-            hdr = header(H, W, int(quality), sampling, int(restart_mcus), tables)
+            hdr = header(H, W, int(quality), sampling, int(restart_mcus), tables, layout)
         scan, st = entropy(coef, int(restart_mcus), tables)
         outs.append(hdr + scan + b"\xff\xd9")
         stats.append(st)
@@ -697,16 +867,18 @@ def reconstruct(coef: np.ndarray, H: int, W: int, quality: int, sampling: str, s
     return np.clip(np.stack([R, G, B], -1), 0, 255).astype(np.uint8)
 
 
-def jpeg_decoded(images, quality: int = 75, sampling: str = "420") -> np.ndarray:
+def jpeg_decoded(images, quality: int = 75, sampling: str = "420", transform: str = "matrix") -> np.ndarray:
     """uint8 ``[B, H, W, 3]`` (or ``[H, W, 3]``) images -> uint8 ``[B, H, W, 3]``: what a libjpeg
-    decoder returns for each image's :func:`jpeg_encode` bytes (any restart interval)."""
+    decoder returns for each image's :func:`jpeg_encode` bytes (any restart interval) with the
+    same ``transform``."""
+    transform_layout(transform)
     arr = images.detach().cpu().numpy() if hasattr(images, "detach") else np.asarray(images)
     if arr.ndim == 3:
         arr = arr[None]
     if arr.ndim != 4 or arr.shape[-1] != 3 or arr.dtype != np.uint8:
         raise ValueError("jpeg_decoded: uint8 [B, H, W, 3] or [H, W, 3] expected")
     _, H, W, _ = arr.shape
-    return np.stack([reconstruct(coefficients(img, int(quality), sampling), H, W, int(quality), sampling)
+    return np.stack([reconstruct(coefficients(img, int(quality), sampling, transform), H, W, int(quality), sampling)
                      for img in arr])
 
 

@@ -113,14 +113,27 @@ def jpeg_huffman(cfg: Config) -> str:
     return h
 
 
+def jpeg_transform(cfg: Config) -> str:
+    """``ModelConfig.jpeg_transform`` (matrix | libjpeg) for ops.jpeg_encode; an unknown value is
+    an error, not the default."""
+    t = str(cfg.model.jpeg_transform).lower()
+    if t not in ("matrix", "libjpeg"):
+        raise ValueError(f"jpeg_transform={cfg.model.jpeg_transform!r}: expected matrix or libjpeg")
+    return t
+
+
 def _jpeg_encode_args(cfg: Config, width: int) -> dict:
-    """jpeg_restart and jpeg_huffman as keyword arguments of ops.jpeg_encode; the default coder and
-    the default tables are not named, so the default configuration makes the call it always made."""
+    """jpeg_restart, jpeg_huffman and jpeg_transform as keyword arguments of ops.jpeg_encode; the
+    default coder, tables and transform are not named, so the default configuration makes the call
+    it always made."""
     restart, entropy = jpeg_restart(cfg, width)
     kw = {"restart_mcus": restart} if entropy == "interval" else {"restart_mcus": restart, "entropy": entropy}
     huffman = jpeg_huffman(cfg)
     if huffman != "standard":
         kw["huffman"] = huffman
+    transform = jpeg_transform(cfg)
+    if transform != "matrix":
+        kw["transform"] = transform
     return kw
 
 
@@ -177,6 +190,7 @@ def build_blur_jpeg_fn(cfg: Config, device: Optional[str] = None):
     from .. import ops
     jpeg_restart(cfg, 16)                   # a bad jpeg_entropy / jpeg_restart_mcus raises here, not per request
     jpeg_huffman(cfg)                       # and so does a bad jpeg_huffman
+    jpeg_transform(cfg)                     # or a bad jpeg_transform
     if kernel == "pil":
         def blur_jpeg_exact(img, radii: Sequence[float], quality: int):
             x = _device_pixels(img, dev)
@@ -214,6 +228,7 @@ def build_content_jpeg_fn(cfg: Config, device: Optional[str] = None):
     from ..game.content import DeviceImage
     jpeg_restart(cfg, 16)                   # a bad jpeg_entropy / jpeg_restart_mcus raises here, not per request
     jpeg_huffman(cfg)                       # and so does a bad jpeg_huffman
+    jpeg_transform(cfg)                     # or a bad jpeg_transform
 
     def content_jpeg(img, quality: int):
         x = img.tensor.to(dev, non_blocking=False)

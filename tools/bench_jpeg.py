@@ -72,6 +72,16 @@ with both tables: their difference is the histogram + table build (and the count
 image's own table).
 
     python tools/bench_jpeg.py --huffman optimized [--blur-kernel pil] [--content] [--out profiles/jpeg_huffman.jsonl]
+
+``--transform libjpeg`` compares ``jpeg_transform=libjpeg`` (libjpeg's forward transform and header
+layout: PIL's file, byte for byte) against the matrix transform in the prewarm (default) or the
+``--content`` mode, both with ``blur_kernel=pil``, ``jpeg_entropy=block`` and no restart markers,
+matrix and libjpeg rows interleaved ``--reps`` times after a warm-up of each; the yardstick is the
+matrix row of the same run.  Per record: host wall time, CPU time, JPEG bytes, the bytes of the
+parent's PIL path for the same pixels and whether the stream equals them; then the device time (HIP
+events, nothing else queued) of the count phase with both transforms.
+
+    python tools/bench_jpeg.py --transform libjpeg [--content] [--out profiles/jpeg_libjpeg.jsonl]
 """
 import argparse
 import io
@@ -125,14 +135,14 @@ def encode_device_ms(batch, restart: int, iters: int = 5):
     best = [1e9, 1e9]
     for _ in range(iters):
         ev[0].record()
-        ext().jpeg_count(batch, tables, header, coef, work, 1, restart)
+        ext().jpeg_count(batch, tables, header, coef, work, 1, restart, 0)
         ev[1].record()
         total = int(work[B].item())
         out = torch.empty(total, device="cuda", dtype=torch.uint8)
         torch.cuda.synchronize()
         t0 = torch.cuda.Event(enable_timing=True)
         t0.record()
-        ext().jpeg_write(batch, tables, header, coef, work, 1, restart, out, total)
+        ext().jpeg_write(batch, tables, header, coef, work, 1, restart, 0, out, total)
         ev[2].record()
         torch.cuda.synchronize()
         best = [min(best[0], ev[0].elapsed_time(ev[1])), min(best[1], t0.elapsed_time(ev[2]))]
@@ -171,13 +181,13 @@ def encode_blocks_device_ms(batch, restart: int, iters: int = 5):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         torch.cuda.synchronize()
         ev[0].record()
-        ext().jpeg_count_blocks(batch, tables, header, coef, work, blk, scratch, stride, 1, restart)
+        ext().jpeg_count_blocks(batch, tables, header, coef, work, blk, scratch, stride, 1, restart, 0)
         ev[1].record()
         total = int(work[B].item())
         out = torch.empty(total + 1, device="cuda", dtype=torch.uint8)
         torch.cuda.synchronize()
         ev[2].record()
-        ext().jpeg_write_blocks(batch, tables, header, coef, work, blk, scratch, stride, 1, restart, out, total)
+        ext().jpeg_write_blocks(batch, tables, header, coef, work, blk, scratch, stride, 1, restart, 0, out, total)
         ev[3].record()
         torch.cuda.synchronize()
         best = [min(best[0], ev[0].elapsed_time(ev[1])), min(best[1], ev[2].elapsed_time(ev[3]))]
@@ -281,7 +291,8 @@ def block_main(a, emit) -> int:
     return 0
 
 
-def count_phase_device_ms(batch, restart: int, entropy: str, optimized: bool, iters: int = 5) -> float:
+def count_phase_device_ms(batch, restart: int, entropy: str, optimized: bool, iters: int = 5,
+                          transform: str = "matrix") -> float:
     """Device time (HIP events; nothing else is queued) of the count phase of ops.jpeg_encode on
     ``batch``: transform (+ histogram + table build with ``optimized``) + the coder's count pass +
     scans, in ms; ``restart`` 0 = no restart markers (block coder)."""
@@ -294,13 +305,15 @@ def count_phase_device_ms(batch, restart: int, entropy: str, optimized: bool, it
     per = min(restart, mx * my) if restart else mx * my
     nint = -(-mx * my // per)
     opt, sfx = (), ""
+    lj, layout = int(transform == "libjpeg"), jf.transform_layout(transform)
     if optimized:
-        tables, header, split = ops._jpeg_opt_plan(batch.device, H, W, QUALITY, "420", restart)
+        tables, header, split = ops._jpeg_opt_plan(batch.device, H, W, QUALITY, "420", restart, layout)
+        dht_cap = 4 + (jf.DHT_EXTRA_PIL if lj else 0) + 4 * (17 + 256)
         opt = (torch.empty(2 * B * 544, device="cuda", dtype=torch.int32),
-               torch.empty(B * (header.numel() + 4 + 4 * (17 + 256)), device="cuda", dtype=torch.uint8), split)
+               torch.empty(B * (header.numel() + dht_cap), device="cuda", dtype=torch.uint8), split)
         sfx = "_opt"
     else:
-        tables, header = ops._jpeg_plan(batch.device, H, W, QUALITY, "420", restart)
+        tables, header = ops._jpeg_plan(batch.device, H, W, QUALITY, "420", restart, layout)
     coef = torch.empty((B, mx * my, nb, 64), device="cuda", dtype=torch.int16)
     block = entropy == "block"
     work = torch.empty(2 * B * nint + B + 1 + int(block) + (B if optimized else 0), device="cuda", dtype=torch.int32)
@@ -315,9 +328,10 @@ def count_phase_device_ms(batch, restart: int, entropy: str, optimized: bool, it
         torch.cuda.synchronize()
         e0.record()
         if block:
-            getattr(ext(), "jpeg_count_blocks" + sfx)(batch, tables, header, coef, work, blk, scratch, stride, 1, restart, *opt)
+            getattr(ext(), "jpeg_count_blocks" + sfx)(batch, tables, header, coef, work, blk, scratch, stride, 1, restart, lj,
+                                                      *opt)
         else:
-            getattr(ext(), "jpeg_count" + sfx)(batch, tables, header, coef, work, 1, restart, *opt)
+            getattr(ext(), "jpeg_count" + sfx)(batch, tables, header, coef, work, 1, restart, lj, *opt)
         e1.record()
         torch.cuda.synchronize()
         best = min(best, e0.elapsed_time(e1))
@@ -388,6 +402,75 @@ def huffman_main(a, emit) -> int:
     return 0
 
 
+def transform_main(a, emit) -> int:
+    """--transform libjpeg: libjpeg's forward transform against the matrix one (see the module text)."""
+    import torch
+    from cassmantle_amd import ops
+    from cassmantle_amd.config import Config
+    from cassmantle_amd.game.content import DeviceImage
+    from cassmantle_amd.game.imaging import BlurCache, encode_jpeg
+    from cassmantle_amd.runtime.factory import build_blur_fn, build_blur_jpeg_fn, build_content_jpeg_fn, jpeg_restart
+
+    def config(transform):
+        c = Config()
+        c.model.gpu_jpeg = c.model.gpu_jpeg_content = True
+        c.model.blur_kernel = "pil"
+        c.model.jpeg_entropy, c.model.jpeg_restart_mcus = "block", -1
+        c.model.jpeg_transform = transform
+        return c
+
+    rows = ("matrix", a.transform)
+    for res in a.res:
+        img = source_image(res).copy()
+        jpeg = encode_jpeg(img, QUALITY)
+        dimg = DeviceImage(torch.from_numpy(img).cuda())
+        dimg.host()
+        blur_fn = build_blur_fn(config("matrix"), "cuda")
+        radii = [i * BUCKET for i in range(1, int(MAX_BLUR / BUCKET) + 1)]
+        mode = "content" if a.content else "prewarm"
+        # the parent's bytes: PIL's encode of the same pixels (prewarm: of PIL's own blur of them)
+        if a.content:
+            parent = [jpeg]
+        else:
+            cache = BlurCache(bucket=BUCKET, quality=QUALITY)
+            cache.set_source("parent", dimg)
+            cache.prewarm("parent", jpeg, MAX_BLUR)
+            parent = [v for (_, r), v in sorted(cache._lru.items()) if r > 0]
+
+        def run(transform, tag):
+            cfg = config(transform)
+            rec = {"res": res, "mode": mode, "blur_kernel": "pil", "entropy": "block", "transform": transform,
+                   "restart_mcus": jpeg_restart(cfg, res)[0]}
+            if a.content:
+                fn = build_content_jpeg_fn(cfg, "cuda")
+                d = DeviceImage(dimg.tensor)
+                torch.cuda.synchronize()
+                w0, c0 = time.perf_counter(), time.process_time()
+                data, _ = fn(d, QUALITY)
+                torch.cuda.synchronize()
+                wall, cpu = time.perf_counter() - w0, time.process_time() - c0
+                outs = [data]
+            else:
+                n, wall, cpu, got = prewarm_once(blur_fn, build_blur_jpeg_fn(cfg, "cuda"), dimg, jpeg, tag)
+                outs = [v for r, v in sorted(got.items()) if r > 0]
+                rec["buckets"] = n
+            rec.update(wall_ms=round(wall * 1e3, 3), cpu_ms=round(cpu * 1e3, 3), jpeg_bytes=sum(len(v) for v in outs),
+                       parent_pil_bytes=sum(len(v) for v in parent), equals_parent_pil_bytes=outs == parent)
+            return rec
+
+        for transform in rows:                          # warm-up of each
+            run(transform, f"warm-{transform}")
+        for rep in range(a.reps):
+            for transform in rows:
+                emit(dict(run(transform, f"{transform}-{rep}"), rep=rep))
+        pixels = dimg.tensor[None].contiguous() if a.content else ops.gaussian_blur_pil(dimg.tensor, radii)
+        cnt = {t: count_phase_device_ms(pixels, 0, "block", False, transform=t) for t in rows}
+        emit({"res": res, "mode": mode, "entropy": "block", "images": int(pixels.shape[0]),
+              "count_phase_device_ms_matrix": round(cnt["matrix"], 4),
+              "count_phase_device_ms_" + a.transform: round(cnt[a.transform], 4)})
+    return 0
+
+
 def reconstruct_device_ms(t, restart: int, iters: int = 5) -> float:
     """Device time of the idct + colour kernels behind ``return_decoded`` for the [1, H, W, 3]
     image ``t`` (HIP events around the two launches; nothing else is queued), in ms."""
@@ -401,7 +484,7 @@ def reconstruct_device_ms(t, restart: int, iters: int = 5) -> float:
     tables, header = ops._jpeg_plan(t.device, H, W, QUALITY, "420", restart)
     coef = torch.empty((B, mx * my, nb, 64), device="cuda", dtype=torch.int16)
     work = torch.empty(2 * B * nint + B + 1, device="cuda", dtype=torch.int32)
-    ext().jpeg_count(t, tables, header, coef, work, 1, restart)
+    ext().jpeg_count(t, tables, header, coef, work, 1, restart, 0)
     planes = torch.empty(coef.numel(), device="cuda", dtype=torch.uint8)
     out = torch.empty((B, H, W, 3), device="cuda", dtype=torch.uint8)
     best = 1e9
@@ -690,6 +773,8 @@ def main(argv=None) -> int:
                     help="the block-parallel entropy coder against the interval coder, prewarm or --content (see above)")
     ap.add_argument("--huffman", choices=["optimized"], default=None,
                     help="the image's own Huffman tables against the standard ones, prewarm or --content (see above)")
+    ap.add_argument("--transform", choices=["libjpeg"], default=None,
+                    help="libjpeg's forward transform against the matrix one, prewarm or --content (see above)")
     ap.add_argument("--jpeg_restart_mcus", type=int, nargs="+", default=[0, 4, -1],
                     help="--entropy block: the settings compared (0: one MCU row, -1: no restart markers)")
     a = ap.parse_args(argv)
@@ -714,6 +799,11 @@ def main(argv=None) -> int:
             sink.write(line + "\n")
             sink.flush()
 
+    if a.transform:
+        rc = transform_main(a, emit)
+        if sink:
+            sink.close()
+        return rc
     if a.entropy or a.huffman:
         rc = huffman_main(a, emit) if a.huffman else block_main(a, emit)
         if sink:
