@@ -822,47 +822,36 @@ def gaussian_blur_pil(img, radii, out: Optional[torch.Tensor] = None):
     return res[0] if scalar else res
 
 
-_JPEG_PLANS: dict = {}     # (device, H, W, quality, sampling, restart_mcus, layout) -> (tables, header) on the device
+_JPEG_PLANS: dict = {}     # (device, H, W, quality, sampling, restart_mcus, layout, optimized) -> (tables, header, split) on the device
 
 
-def _jpeg_plan(device, H: int, W: int, quality: int, sampling: str, restart_mcus: int, layout: str = "compact"):
-    """The encoder's constant inputs on ``device``: int32 [128 + 544] quantisation | Huffman tables
-    and the uint8 header bytes (SOI .. SOS) in the header ``layout``, uploaded once per key."""
+def _jpeg_plan(device, H: int, W: int, quality: int, sampling: str, restart_mcus: int, layout: str = "compact",
+               optimized: bool = False):
+    """The encoder's constant inputs on ``device``, uploaded once per key: int32 [128 + 544]
+    quantisation | Huffman tables, the uint8 header bytes (SOI .. SOS) in the header ``layout``,
+    and 0.  ``optimized`` (the image's own Huffman tables: the standard words are not read): the
+    header without its DHT segment, the bytes before it followed by those behind it, and the
+    length of the first part."""
     from . import jpeg_format as jf
-    key = (device, H, W, quality, sampling, restart_mcus, layout)
+    key = (device, H, W, quality, sampling, restart_mcus, layout, optimized)
     plan = _JPEG_PLANS.get(key)
     if plan is None:
         import numpy as np
-        hdr = jf.header(H, W, quality, sampling, restart_mcus, None, layout)
+        pre, suf = jf.header_parts(H, W, quality, sampling, restart_mcus, layout)
+        hdr = pre + suf if optimized else jf.header(H, W, quality, sampling, restart_mcus, None, layout)
         lq, cq = jf.quant_tables(quality)
         tables = np.concatenate([np.asarray(lq + cq, dtype=np.int32), jf.huff_table()])
         if len(_JPEG_PLANS) >= 64:
             _JPEG_PLANS.clear()
         plan = _JPEG_PLANS[key] = (torch.from_numpy(tables).to(device),
-                                   torch.frombuffer(bytearray(hdr), dtype=torch.uint8).to(device))
+                                   torch.frombuffer(bytearray(hdr), dtype=torch.uint8).to(device),
+                                   len(pre) if optimized else 0)
     return plan
 
 
 JPEG_ENTROPY_CODERS = ("interval", "block")
 JPEG_HUFFMAN_MODES = ("standard", "optimized")
 JPEG_TRANSFORMS = ("matrix", "libjpeg")
-_JPEG_OPT_PLANS: dict = {}     # (device, H, W, quality, sampling, restart_mcus, layout) -> (tables, header parts, split) on the device
-
-
-def _jpeg_opt_plan(device, H: int, W: int, quality: int, sampling: str, restart_mcus: int, layout: str = "compact"):
-    """The constant inputs of an encode with optimised Huffman tables: the tables of
-    :func:`_jpeg_plan` (their Huffman words are not read), the header bytes before the DHT segment
-    followed by those behind it, and the length of the first part."""
-    from . import jpeg_format as jf
-    key = (device, H, W, quality, sampling, restart_mcus, layout)
-    plan = _JPEG_OPT_PLANS.get(key)
-    if plan is None:
-        pre, suf = jf.header_parts(H, W, quality, sampling, restart_mcus, layout)
-        if len(_JPEG_OPT_PLANS) >= 64:
-            _JPEG_OPT_PLANS.clear()
-        plan = _JPEG_OPT_PLANS[key] = (_jpeg_plan(device, H, W, quality, sampling, restart_mcus, layout)[0],
-                                       torch.frombuffer(bytearray(pre + suf), dtype=torch.uint8).to(device), len(pre))
-    return plan
 
 
 def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: int = 4,
@@ -932,63 +921,44 @@ def jpeg_encode(images, quality: int = 75, sampling: str = "420", restart_mcus: 
         raise ValueError("jpeg_encode: restart_mcus >= 0")
     B, H, W, _ = t.shape
     _, nb, mx, my = jf.geometry(H, W, sampling)
-    optimized = huffman == "optimized"
+    blocks, optimized = entropy == "block", huffman == "optimized"
     lj = int(transform == "libjpeg")
-    layout = jf.transform_layout(transform)
-    opt, nopt, sfx = (), 0, ""
     if optimized:
-        # the image's tables and header are built on the device: counts | code words, headers
         jf.check_count_range(mx * my * nb)
         if B > 65535:
             raise ValueError("jpeg_encode: at most 65535 images per call with optimised Huffman tables")
-        tables, header, split = _jpeg_opt_plan(t.device, H, W, quality, sampling, restart_mcus, layout)
-        hopt = torch.empty(2 * B * 544, device=t.device, dtype=torch.int32)
-        # room for every image's DHT: one segment header, or four in the PIL layout
-        dht_cap = 4 + (jf.DHT_EXTRA_PIL if lj else 0) + 4 * (17 + 256)
-        hdrs = torch.empty(B * (header.numel() + dht_cap), device=t.device, dtype=torch.uint8)
-        opt, nopt, sfx = (hopt, hdrs, split), B, "_opt"
-    else:
-        tables, header = _jpeg_plan(t.device, H, W, quality, sampling, restart_mcus, layout)
+    tables, header, split = _jpeg_plan(t.device, H, W, quality, sampling, restart_mcus, jf.transform_layout(transform),
+                                       optimized)
     t = t.contiguous()
-    per = min(restart_mcus, mx * my) if restart_mcus else mx * my          # MCUs per interval
-    nint = (mx * my + per - 1) // per
-    coef = torch.empty((B, mx * my, nb, 64), device=t.device, dtype=torch.int16)
     s420 = int(sampling == "420")
-    if entropy == "block":
-        # an interval's unstuffed string has a slot for the worst case of every block; only the
-        # words blocks start in are zeroed (by the scan pass), nothing here
-        bound = jf.block_bits_bound_optimized() if optimized else jf.block_bits_bound()
-        stride = (per * nb * bound + 31) // 32
-        work = torch.empty(2 * B * nint + B + 2 + nopt, device=t.device, dtype=torch.int32)
-        blk = torch.empty(B * mx * my * nb + B * nint, device=t.device, dtype=torch.int32)
-        scratch = torch.empty(B * nint * stride, device=t.device, dtype=torch.int32)
-        getattr(ext(), "jpeg_count_blocks" + sfx)(t, tables, header, coef, work, blk, scratch, stride, s420,
-                                                  restart_mcus, lj, *opt)
-        # device-to-host copy 1: the image offsets + the error word (+ the header lengths)
-        base = work[: B + 2 + nopt].cpu().tolist()
-        hdr_lens, base = base[B + 2:], base[: B + 2]
-        if base.pop():
-            raise RuntimeError("jpeg_encode: the block coder refused a scratch index (a block over the bits bound)")
-        if not all(hdr_lens):
-            raise ValueError("jpeg: a Huffman code longer than 32 bits")
-        out = torch.empty(base[-1] + 1, device=t.device, dtype=torch.uint8)
-        getattr(ext(), "jpeg_write_blocks" + sfx)(t, tables, header, coef, work, blk, scratch, stride, s420,
-                                                  restart_mcus, lj, out, base[-1], *opt)
-        host = out.cpu().numpy()                      # device-to-host copy 2: the payload + the error byte
-        if host[-1]:
-            raise RuntimeError("jpeg_encode: the block coder refused a payload index")
-        mv = memoryview(host)
-    else:
-        work = torch.empty(2 * B * nint + B + 1 + nopt, device=t.device, dtype=torch.int32)
-        getattr(ext(), "jpeg_count" + sfx)(t, tables, header, coef, work, s420, restart_mcus, lj, *opt)
-        # device-to-host copy 1: the image offsets (+ the header lengths)
-        base = work[: B + 1 + nopt].cpu().tolist()
-        hdr_lens, base = base[B + 1:], base[: B + 1]
-        if not all(hdr_lens):
-            raise ValueError("jpeg: a Huffman code longer than 32 bits")
-        out = torch.empty(base[-1], device=t.device, dtype=torch.uint8)
-        getattr(ext(), "jpeg_write" + sfx)(t, tables, header, coef, work, s420, restart_mcus, lj, out, base[-1], *opt)
-        mv = memoryview(out.cpu().numpy())                # device-to-host copy 2: the payload
+    try:
+        lay = ext().jpeg_encode_layout(B, H, W, s420, restart_mcus, blocks, optimized, lj, header.numel())
+    except ValueError as e:                  # a size limit: the error the encode bindings raise for it
+        raise RuntimeError(str(e)) from None
+
+    def buf(name, dtype=torch.int32):
+        return torch.empty(lay[name], device=t.device, dtype=dtype)
+    coef, work = buf("coef", torch.int16), buf("work")
+    # block coder: an interval's unstuffed string has a slot for the worst case of every block; only
+    # the words blocks start in are zeroed (by the scan pass), nothing here
+    blk, scratch = (buf("blk"), buf("scratch")) if blocks else (None, None)
+    # optimised tables: the image's tables and header are built on the device: counts | code words, headers
+    hopt, hdrs = (buf("hopt"), buf("hdrs", torch.uint8)) if optimized else (None, None)
+    args = (t, tables, header, coef, work, s420, restart_mcus, lj, blk, scratch, hopt, hdrs, split)
+    ext().jpeg_count(*args)
+    # device-to-host copy 1: the image offsets (+ the block coder's error word) (+ the header lengths)
+    head = work[: lay["prefix"]].cpu().tolist()
+    base = head[: B + 1]
+    if blocks and head[lay["err"]]:
+        raise RuntimeError("jpeg_encode: the block coder refused a scratch index (a block over the bits bound)")
+    if optimized and not all(head[lay["hdr_lens"]: lay["hdr_lens"] + B]):
+        raise ValueError("jpeg: a Huffman code longer than 32 bits")
+    out = torch.empty(base[-1] + lay["slack"], device=t.device, dtype=torch.uint8)
+    ext().jpeg_write(*args, out, base[-1])
+    host = out.cpu().numpy()                  # device-to-host copy 2: the payload (+ the block coder's error byte)
+    if blocks and host[-1]:
+        raise RuntimeError("jpeg_encode: the block coder refused a payload index")
+    mv = memoryview(host)
     outs = [bytes(mv[base[i]: base[i + 1]]) for i in range(B)]
     if not return_decoded:
         return outs
@@ -1022,12 +992,12 @@ def _jpeg_decode_plan(device, stream):
     return plan
 
 
-def _jpeg_decode_inputs(streams, device, extra=None):
+def _jpeg_decode_inputs(streams, device, extra=()):
     """The device inputs of one decode of parsed ``streams`` (one header key): the staged uint8
     buffer (interval table, then every stream's entropy-coded segment, scan start .. EOI) after its
-    one non-blocking copy from pinned memory, the number of bytes behind the table, the tables.
-    ``extra``: uint32 words staged behind the (padded) bytes in the same copy; their byte offset is
-    returned as a fourth value."""
+    one non-blocking copy from pinned memory, the number of bytes behind the table, the tables,
+    and the padded length of table and bytes: the byte offset of ``extra``, uint32 words staged
+    behind them in the same copy (``()``: none)."""
     import numpy as np
     s0 = streams[0]
     B, nint = len(streams), len(s0.intervals)
@@ -1043,21 +1013,18 @@ def _jpeg_decode_inputs(streams, device, extra=None):
     if base >= 2 ** 32 - 1:
         raise ValueError("jpeg_decode: batch too large for 32-bit byte offsets")
     nstage = (8 * B * nint + base + 15) // 16 * 16           # padded: word reads stay inside
-    nextra = 0 if extra is None else 4 * extra.size
-    stage = torch.empty(nstage + nextra, dtype=torch.uint8, pin_memory=True)
+    extra = np.ascontiguousarray(extra, dtype=np.uint32).reshape(-1)
+    stage = torch.empty(nstage + 4 * extra.size, dtype=torch.uint8, pin_memory=True)
     host = stage.numpy()
-    if extra is not None:
-        host[nstage:] = np.ascontiguousarray(extra, dtype=np.uint32).reshape(-1).view(np.uint8)
-        host = host[:nstage]
+    host[nstage:] = extra.view(np.uint8)
+    host = host[:nstage]
     host[: 8 * B * nint] = ivals.reshape(-1).view(np.uint8)
     p = 8 * B * nint
     for seg in segs:
         host[p: p + len(seg)] = np.frombuffer(seg, dtype=np.uint8)
         p += len(seg)
     host[p:] = 0
-    if extra is not None:
-        return stage.to(device, non_blocking=True), base, _jpeg_decode_plan(device, s0), nstage
-    return stage.to(device, non_blocking=True), base, _jpeg_decode_plan(device, s0)
+    return stage.to(device, non_blocking=True), base, _jpeg_decode_plan(device, s0), nstage
 
 
 def _jpeg_chunk_groups(lens, cb: int):
@@ -1158,55 +1125,41 @@ def jpeg_decode(data, device=None, out=None, mode="interval", chunk_bytes=32, in
         res = torch.from_numpy(px[0] if single else px).to(dev)
         return res if out is None else out.copy_(res)
     _, nb, mx, my = jf.geometry(H, W, s0.sampling)
+    device, ncoef, s420 = probe.device, B * mx * my * nb * 64, int(s0.sampling == "420")
+    sync = ()
     if chunked:
-        return _jpeg_decode_chunked(streams, probe.device, out, single, cb, info)
-    staged, base, tables = _jpeg_decode_inputs(streams, probe.device)
-    ncoef = B * mx * my * nb * 64
-    buf = torch.empty(ncoef + 8, device=probe.device, dtype=torch.int16)
-    s420 = int(s0.sampling == "420")
-    ext().jpeg_entropy_decode(staged, base, tables, buf, B, H, W, s420, s0.restart)
-    planes = torch.empty(ncoef, device=probe.device, dtype=torch.uint8)
-    res = out if out is not None else torch.empty((H, W, 3) if single else (B, H, W, 3),
-                                                  device=probe.device, dtype=torch.uint8)
-    ext().jpeg_reconstruct(buf[:ncoef].view(B, mx * my, nb, 64), tables[:672], planes, res.view(B, H, W, 3),
-                           H, W, s420)
-    status = int(buf[ncoef: ncoef + 4].view(torch.int64).cpu().item()) & (2 ** 64 - 1)      # the only sync
-    if status:
-        jf.raise_status(status & 0xFFFFFFFF, 0xFFFFFFFF - (status >> 32))
-    return res
-
-
-def _jpeg_decode_chunked(streams, device, out, single, cb, info):
-    """The HIP path of ``jpeg_decode(mode="chunked")`` on the current stream."""
-    from . import jpeg_format as jf
-    import numpy as np
-    s0 = streams[0]
-    B, H, W = len(streams), s0.H, s0.W
-    _, nb, mx, my = jf.geometry(H, W, s0.sampling)
-    lens = np.asarray([[ln for _, ln in s.intervals] for s in streams], dtype=np.int64)
-    lane0, groups, threads, chunks = _jpeg_chunk_groups(lens, cb)
-    staged, base, tables, extra = _jpeg_decode_inputs(streams, device, np.concatenate([lane0, groups.reshape(-1)]))
-    ncoef = B * mx * my * nb * 64
-    buf = torch.empty(ncoef + 16, device=device, dtype=torch.int16)
-    s420 = int(s0.sampling == "420")
-    ext().jpeg_entropy_decode_chunked(staged, base, tables, buf, B, H, W, s420, s0.restart, extra, len(groups), cb,
-                                      threads)
+        lens = np.asarray([[ln for _, ln in s.intervals] for s in streams], dtype=np.int64)
+        lane0, groups, threads, chunks = _jpeg_chunk_groups(lens, cb)
+        sync = np.concatenate([lane0, groups.reshape(-1)])
+    staged, base, tables, extra = _jpeg_decode_inputs(streams, device, sync)
+    buf = torch.empty(ncoef + (16 if chunked else 8), device=device, dtype=torch.int16)
     planes = torch.empty(ncoef, device=device, dtype=torch.uint8)
     res = out if out is not None else torch.empty((H, W, 3) if single else (B, H, W, 3), device=device,
                                                   dtype=torch.uint8)
-    coef = buf[:ncoef].view(B, mx * my, nb, 64)
-    ext().jpeg_reconstruct(coef, tables[:672], planes, res.view(B, H, W, 3), H, W, s420)
+
+    def reconstruct():
+        ext().jpeg_reconstruct(buf[:ncoef], tables[:672], planes, res.view(B, H, W, 3), H, W, s420)
+
+    def decode_intervals():              # the interval kernel, its pixels, its status word: what is raised
+        ext().jpeg_entropy_decode(staged, base, tables, buf[: ncoef + 8], B, H, W, s420, s0.restart)
+        reconstruct()
+        status = int(buf[ncoef: ncoef + 4].view(torch.int64).cpu().item()) & (2 ** 64 - 1)
+        if status:
+            jf.raise_status(status & 0xFFFFFFFF, 0xFFFFFFFF - (status >> 32))
+
+    if not chunked:
+        decode_intervals()               # its status read is the only sync
+        return res
+    ext().jpeg_entropy_decode_chunked(staged, base, tables, buf, B, H, W, s420, s0.restart, extra, len(groups), cb,
+                                      threads)
+    reconstruct()
     # the only sync of a stream that decodes: status (0 here), flag, rounds, blocks completed
     words = buf[ncoef: ncoef + 16].view(torch.int32).cpu().tolist()
     fallback = bool(words[2]) or (words[4] & 0xFFFFFFFF) != B * mx * my * nb
     if info is not None:
         info.update(chunks=chunks, rounds=words[3], chunk_bytes=cb, serial_fallback=fallback)
     if fallback:                         # the interval kernel decides what the stream's fault is called
-        ext().jpeg_entropy_decode(staged, base, tables, buf[: ncoef + 8], B, H, W, s420, s0.restart)
-        ext().jpeg_reconstruct(coef, tables[:672], planes, res.view(B, H, W, 3), H, W, s420)
-        status = int(buf[ncoef: ncoef + 4].view(torch.int64).cpu().item()) & (2 ** 64 - 1)
-        if status:
-            jf.raise_status(status & 0xFFFFFFFF, 0xFFFFFFFF - (status >> 32))
+        decode_intervals()
     return res
 
 

@@ -8,6 +8,7 @@
 #include <hip/hip_ext.h>
 
 #include "gemm_tiles.h"
+#include "jpeg_layout.h"
 #include "kernels.h"
 
 namespace {
@@ -861,183 +862,118 @@ void decode_attention(const at::Tensor& q, const at::Tensor& k_cache, const at::
 
 // Batched JPEG encode, phase 1 / 2 (ops.jpeg_encode allocates: the payload size is known only
 // after phase 1's offsets reach the host).  tables: int32 [128 + 544] = quantisation | Huffman.
-// blocks: the block-parallel coder's call: restart 0 = no restart markers (one interval), and work has
-// one more word behind base (the error word)
-// opt: the buffers of the optimised Huffman tables (jpeg.hip: optimised Huffman tables): hopt int32
-// [2 * B * 544] = symbol counts | every image's code words, hdrs uint8 [B * cap] every image's
-// header, cap = header bytes + 4 + 4 * (17 + 256); header = the bytes before the DHT segment
-// (split of them) followed by those behind it; work has B more words behind base (and the error
-// word): every image's header length
-// lj: 1 = the libjpeg forward contract (jpeg.hip): its transform kernel; with opt the four DHT
-// segments of its header layout, so cap = header bytes + 4 * 4 + 4 * (17 + 256)
-struct JpegOptBufs {
-  at::Tensor hopt, hdrs;
-  int64_t split = 0;
+// Every buffer's size and the words of work come from jpeg_encode_layout (jpeg_layout.h).
+// blk + scratch: the block-parallel coder (jpeg.hip: block-parallel entropy coder), where restart
+// 0 = no restart markers (one interval).  hopt + hdrs + split: optimised Huffman tables (jpeg.hip:
+// optimised Huffman tables); header = the bytes before the DHT segment (split of them) followed
+// by those behind it.  lj: 1 = the libjpeg forward contract (jpeg.hip): its transform kernel;
+// with optimised tables the four DHT segments of its header layout.
+using OptTensor = c10::optional<at::Tensor>;
+
+struct JpegEncodeCall {
+  JpegArgs a;
+  JpegBlkArgs k;
+  bool blocks = false;
 };
 
-JpegArgs jpeg_args(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                   at::Tensor& work, int64_t s420, int64_t restart, int64_t lj, bool blocks = false,
-                   const JpegOptBufs* opt = nullptr) {
+JpegEncodeCall jpeg_args(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
+                         at::Tensor& work, int64_t s420, int64_t restart, int64_t lj, const OptTensor& blk,
+                         const OptTensor& scratch, const OptTensor& hopt, const OptTensor& hdrs, int64_t split) {
   CHECK_DEV(images); CHECK_CONTIG(images); CHECK_DEV(tables); CHECK_CONTIG(tables); CHECK_DEV(header);
   CHECK_CONTIG(header); CHECK_DEV(coef); CHECK_CONTIG(coef); CHECK_DEV(work); CHECK_CONTIG(work);
+  TORCH_CHECK(blk.has_value() == scratch.has_value(), "jpeg: the block coder takes blk and scratch together");
+  TORCH_CHECK(hopt.has_value() == hdrs.has_value() && (hopt.has_value() || split == 0),
+              "jpeg: optimised Huffman tables take hopt, hdrs and split together");
   TORCH_CHECK(images.scalar_type() == at::kByte && images.dim() == 4 && images.size(3) == 3 && images.numel() > 0,
               "jpeg: images uint8 [B, H, W, 3]");
   TORCH_CHECK(tables.scalar_type() == at::kInt && tables.numel() == 128 + 544, "jpeg: tables int32 [672]");
   TORCH_CHECK(header.scalar_type() == at::kByte && header.numel() > 0, "jpeg: header uint8");
-  if (blocks) {
-    TORCH_CHECK(restart >= 0 && restart < 65536, "jpeg: restart_mcus 0..65535");
-  } else {
-    TORCH_CHECK(restart >= 1 && restart < 65536, "jpeg: the HIP encoder needs 1 <= restart_mcus <= 65535");
-  }
   TORCH_CHECK(lj == 0 || lj == 1, "jpeg: lj 0 (matrix transform) or 1 (libjpeg forward contract)");
-  JpegArgs a;
+  JpegEncodeCall c;
+  c.blocks = blk.has_value();
+  const JpegEncodeLayout l = jpeg_encode_layout(images.size(0), images.size(1), images.size(2), s420 != 0, restart, c.blocks,
+                                                hopt.has_value(), lj != 0, header.numel());
+  TORCH_CHECK(l.refusal == nullptr, l.refusal);
+  TORCH_CHECK(coef.scalar_type() == at::kShort && coef.numel() == l.coef, "jpeg: coef int16 [B, mcus, blocks, 64]");
+  TORCH_CHECK(work.scalar_type() == at::kInt && work.numel() == l.work,
+              "jpeg: work int32 [2 * B * intervals + B + 1 (+ 1 with the block coder) (+ B with optimised tables)]");
+  JpegArgs& a = c.a;
   a.lj = (int)lj;
   a.img = images.data_ptr<uint8_t>();
   a.B = (int)images.size(0); a.H = (int)images.size(1); a.W = (int)images.size(2);
-  TORCH_CHECK(a.H < 65536 && a.W < 65536, "jpeg: image sides must be below 65536");
-  const int mcu = s420 ? 16 : 8;
-  a.nb = s420 ? 6 : 3;
-  a.mx = (a.W + mcu - 1) / mcu; a.my = (a.H + mcu - 1) / mcu;
-  const long long mcus = (long long)a.mx * a.my;
-  if (restart == 0) restart = mcus;                  // blocks only: the whole image is one interval
-  a.restart = (int)restart;
-  a.nint = (int)((mcus + restart - 1) / restart);
+  a.nb = l.g.nb; a.mx = l.g.mx; a.my = l.g.my;
+  a.restart = (int)l.g.restart;
+  a.nint = (int)l.g.nint;
   a.hdr_len = (int)header.numel();
-  const int hdr_cap = a.hdr_len + (opt ? (lj ? 4 * 4 : 4) + 4 * (17 + 256) : 0);
-  // 32-bit payload offsets: bound by the coder's worst case (20 + 63 * 26 bits per block, 27 + 63 * 26
-  // with optimised tables, every byte stuffed, one padding byte and one marker per interval)
-  TORCH_CHECK((double)a.B * ((double)hdr_cap + (double)mcus * a.nb * (opt ? 417 : 416) + (double)a.nint * 3) < 2147483648.0,
-              "jpeg: batch too large for 32-bit payload offsets");
-  TORCH_CHECK(coef.scalar_type() == at::kShort && coef.numel() == (long long)a.B * mcus * a.nb * 64,
-              "jpeg: coef int16 [B, mcus, blocks, 64]");
-  const int extra = (blocks ? 1 : 0) + (opt ? a.B : 0);
-  TORCH_CHECK(work.scalar_type() == at::kInt && work.numel() == 2LL * a.B * a.nint + a.B + 1 + extra,
-              "jpeg: work int32 [2 * B * intervals + B + 1 (+ 1 with the block coder) (+ B with optimised tables)]");
   a.qtab = tables.data_ptr<int>(); a.huff = a.qtab + 128;
   a.header = header.data_ptr<uint8_t>();
   a.coef = coef.data_ptr<int16_t>();
   a.base = reinterpret_cast<uint32_t*>(work.data_ptr<int>());     // [B + 1] first: what the host reads
-  a.lens = a.base + a.B + 1 + extra;
-  a.offs = a.lens + (long long)a.B * a.nint;
-  if (opt) {
-    CHECK_DEV(opt->hopt); CHECK_CONTIG(opt->hopt); CHECK_DEV(opt->hdrs); CHECK_CONTIG(opt->hdrs);
-    TORCH_CHECK(a.B <= 65535, "jpeg: at most 65535 images per call with optimised Huffman tables");
-    TORCH_CHECK(mcus * a.nb * 64 < 2147483648LL, "jpeg: optimised Huffman tables count symbols in 32-bit words");
-    TORCH_CHECK(opt->split > 0 && opt->split < a.hdr_len, "jpeg: header = bytes before the DHT segment | bytes behind it");
-    TORCH_CHECK(opt->hopt.scalar_type() == at::kInt && opt->hopt.numel() == 2LL * a.B * 544, "jpeg: hopt int32 [2 * B * 544]");
-    TORCH_CHECK(opt->hdrs.scalar_type() == at::kByte && opt->hdrs.numel() == (long long)a.B * hdr_cap,
+  a.lens = a.base + l.lens;
+  a.offs = a.base + l.offs;
+  if (hopt.has_value()) {
+    CHECK_DEV(*hopt); CHECK_CONTIG(*hopt); CHECK_DEV(*hdrs); CHECK_CONTIG(*hdrs);
+    TORCH_CHECK(split > 0 && split < a.hdr_len, "jpeg: header = bytes before the DHT segment | bytes behind it");
+    TORCH_CHECK(hopt->scalar_type() == at::kInt && hopt->numel() == l.hopt, "jpeg: hopt int32 [2 * B * 544]");
+    TORCH_CHECK(hdrs->scalar_type() == at::kByte && hdrs->numel() == l.hdrs,
                 "jpeg: hdrs uint8 [B * (header bytes + 4 (lj: 16) + 4 * (17 + 256))]");
-    a.freq = reinterpret_cast<uint32_t*>(opt->hopt.data_ptr<int>());
-    a.ihuff = a.freq + (long long)a.B * 544;
-    a.hdrs = opt->hdrs.data_ptr<uint8_t>();
-    a.hdr_cap = hdr_cap;
-    a.hdr_split = (int)opt->split;
-    a.hdr_lens = a.base + a.B + 1 + (blocks ? 1 : 0);
+    a.freq = reinterpret_cast<uint32_t*>(hopt->data_ptr<int>());
+    a.ihuff = a.freq + l.hopt / 2;
+    a.hdrs = hdrs->data_ptr<uint8_t>();
+    a.hdr_cap = (int)l.hdr_cap;
+    a.hdr_split = (int)split;
+    a.hdr_lens = a.base + l.hdr_lens;
   }
-  return a;
-}
-
-// The block-parallel coder's buffers (jpeg.hip: block-parallel entropy coder).  blk int32
-// [B * mcus * blocks + B * intervals] = bits | ubits; scratch int32 [B * intervals * stride].
-JpegBlkArgs jpeg_blk_args(const JpegArgs& a, at::Tensor& work, at::Tensor& blk, at::Tensor& scratch, int64_t stride) {
-  const int max_bits = a.ihuff != nullptr ? jpeg_blk_max_bits_optimized() : jpeg_blk_max_bits();
-  CHECK_DEV(blk); CHECK_CONTIG(blk); CHECK_DEV(scratch); CHECK_CONTIG(scratch);
-  const long long mcus = (long long)a.mx * a.my, nblk = (long long)a.B * mcus * a.nb, nivals = (long long)a.B * a.nint;
-  const long long per = (a.restart < mcus ? (long long)a.restart : mcus) * a.nb;
-  // bit offsets within an interval are 32-bit words; the slot holds the worst case of every block
-  TORCH_CHECK((double)per * max_bits < 4294967296.0, "jpeg: restart interval too long for 32-bit bit offsets");
-  TORCH_CHECK(stride == (per * max_bits + 31) / 32 && stride < (1LL << 30),
-              "jpeg: stride = ceil(blocks per interval * max bits per block / 32)");
-  TORCH_CHECK(nblk < 256LL * 2147483647LL && nivals < 2147483647LL, "jpeg: batch too large for one launch");
-  TORCH_CHECK(blk.scalar_type() == at::kInt && blk.numel() == nblk + nivals, "jpeg: blk int32 [B * mcus * blocks + B * intervals]");
-  TORCH_CHECK(scratch.scalar_type() == at::kInt && scratch.numel() == nivals * stride,
-              "jpeg: scratch int32 [B * intervals * stride]");
-  JpegBlkArgs k;
-  k.bits = reinterpret_cast<uint32_t*>(blk.data_ptr<int>());
-  k.ubits = k.bits + nblk;
-  k.scratch = reinterpret_cast<uint32_t*>(scratch.data_ptr<int>());
-  k.stride = (uint32_t)stride;
-  k.err = reinterpret_cast<uint32_t*>(work.data_ptr<int>()) + a.B + 1;
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.coef) % 16 == 0, "jpeg: coef must be 16-byte aligned");
-  return k;
-}
-
-void jpeg_count_blocks(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                       at::Tensor& work, at::Tensor& blk, at::Tensor& scratch, int64_t stride, int64_t s420,
-                       int64_t restart, int64_t lj) {
-  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, lj, true);
-  launch_jpeg_count_blocks(a, jpeg_blk_args(a, work, blk, scratch, stride), cur_stream());
-}
-
-// out uint8 [total + 1]: the payload and, behind it, the write pass's error byte
-void jpeg_write_blocks(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                       at::Tensor& work, at::Tensor& blk, at::Tensor& scratch, int64_t stride, int64_t s420,
-                       int64_t restart, int64_t lj, at::Tensor& out, int64_t total) {
-  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, lj, true);
-  JpegBlkArgs k = jpeg_blk_args(a, work, blk, scratch, stride);
-  CHECK_DEV(out); CHECK_CONTIG(out);
-  TORCH_CHECK(out.scalar_type() == at::kByte && total > 0 && total < 2147483647LL && out.numel() == total + 1,
-              "jpeg: out uint8 [base[B] + 1]");
-  a.out = out.data_ptr<uint8_t>();
-  k.out_size = (uint32_t)total;
-  launch_jpeg_write_blocks(a, k, cur_stream());
+  if (c.blocks) {
+    CHECK_DEV(*blk); CHECK_CONTIG(*blk); CHECK_DEV(*scratch); CHECK_CONTIG(*scratch);
+    TORCH_CHECK(blk->scalar_type() == at::kInt && blk->numel() == l.blk, "jpeg: blk int32 [B * mcus * blocks + B * intervals]");
+    TORCH_CHECK(scratch->scalar_type() == at::kInt && scratch->numel() == l.scratch,
+                "jpeg: scratch int32 [B * intervals * stride]");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(a.coef) % 16 == 0, "jpeg: coef must be 16-byte aligned");
+    JpegBlkArgs& k = c.k;
+    k.bits = reinterpret_cast<uint32_t*>(blk->data_ptr<int>());
+    k.ubits = k.bits + l.coef / 64;
+    k.scratch = reinterpret_cast<uint32_t*>(scratch->data_ptr<int>());
+    k.stride = (uint32_t)l.stride;
+    k.err = a.base + l.err;
+  }
+  return c;
 }
 
 void jpeg_count(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                at::Tensor& work, int64_t s420, int64_t restart, int64_t lj) {
-  launch_jpeg_count(jpeg_args(images, tables, header, coef, work, s420, restart, lj), cur_stream());
+                at::Tensor& work, int64_t s420, int64_t restart, int64_t lj, const OptTensor& blk, const OptTensor& scratch,
+                const OptTensor& hopt, const OptTensor& hdrs, int64_t split) {
+  const JpegEncodeCall c = jpeg_args(images, tables, header, coef, work, s420, restart, lj, blk, scratch, hopt, hdrs, split);
+  if (c.blocks) launch_jpeg_count_blocks(c.a, c.k, cur_stream());
+  else launch_jpeg_count(c.a, cur_stream());
 }
 
+// total = base[B] as read back by the caller: every store of the write pass lands below it.  The
+// block coder's out has one more byte, the write pass's error byte.
 void jpeg_write(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                at::Tensor& work, int64_t s420, int64_t restart, int64_t lj, at::Tensor& out, int64_t total) {
-  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, lj);
+                at::Tensor& work, int64_t s420, int64_t restart, int64_t lj, const OptTensor& blk, const OptTensor& scratch,
+                const OptTensor& hopt, const OptTensor& hdrs, int64_t split, at::Tensor& out, int64_t total) {
+  JpegEncodeCall c = jpeg_args(images, tables, header, coef, work, s420, restart, lj, blk, scratch, hopt, hdrs, split);
   CHECK_DEV(out); CHECK_CONTIG(out);
-  // total = base[B] as read back by the caller: every store of the write pass lands below it
-  TORCH_CHECK(out.scalar_type() == at::kByte && total > 0 && out.numel() == total, "jpeg: out uint8 [base[B]]");
-  a.out = out.data_ptr<uint8_t>();
-  launch_jpeg_write(a, cur_stream());
+  TORCH_CHECK(out.scalar_type() == at::kByte && total > 0 && total < 2147483647LL && out.numel() == total + (c.blocks ? 1 : 0),
+              c.blocks ? "jpeg: out uint8 [base[B] + 1]" : "jpeg: out uint8 [base[B]]");
+  c.a.out = out.data_ptr<uint8_t>();
+  c.k.out_size = (uint32_t)total;
+  if (c.blocks) launch_jpeg_write_blocks(c.a, c.k, cur_stream());
+  else launch_jpeg_write(c.a, cur_stream());
 }
 
-// The same four calls with optimised Huffman tables (JpegOptBufs above).
-void jpeg_count_blocks_opt(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                           at::Tensor& work, at::Tensor& blk, at::Tensor& scratch, int64_t stride, int64_t s420,
-                           int64_t restart, int64_t lj, at::Tensor& hopt, at::Tensor& hdrs, int64_t split) {
-  const JpegOptBufs opt{hopt, hdrs, split};
-  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, lj, true, &opt);
-  launch_jpeg_count_blocks(a, jpeg_blk_args(a, work, blk, scratch, stride), cur_stream());
-}
-
-void jpeg_write_blocks_opt(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                           at::Tensor& work, at::Tensor& blk, at::Tensor& scratch, int64_t stride, int64_t s420,
-                           int64_t restart, int64_t lj, at::Tensor& out, int64_t total, at::Tensor& hopt,
-                           at::Tensor& hdrs, int64_t split) {
-  const JpegOptBufs opt{hopt, hdrs, split};
-  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, lj, true, &opt);
-  JpegBlkArgs k = jpeg_blk_args(a, work, blk, scratch, stride);
-  CHECK_DEV(out); CHECK_CONTIG(out);
-  TORCH_CHECK(out.scalar_type() == at::kByte && total > 0 && total < 2147483647LL && out.numel() == total + 1,
-              "jpeg: out uint8 [base[B] + 1]");
-  a.out = out.data_ptr<uint8_t>();
-  k.out_size = (uint32_t)total;
-  launch_jpeg_write_blocks(a, k, cur_stream());
-}
-
-void jpeg_count_opt(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                    at::Tensor& work, int64_t s420, int64_t restart, int64_t lj, at::Tensor& hopt, at::Tensor& hdrs,
-                    int64_t split) {
-  const JpegOptBufs opt{hopt, hdrs, split};
-  launch_jpeg_count(jpeg_args(images, tables, header, coef, work, s420, restart, lj, false, &opt), cur_stream());
-}
-
-void jpeg_write_opt(const at::Tensor& images, const at::Tensor& tables, const at::Tensor& header, at::Tensor& coef,
-                    at::Tensor& work, int64_t s420, int64_t restart, int64_t lj, at::Tensor& out, int64_t total,
-                    at::Tensor& hopt, at::Tensor& hdrs, int64_t split) {
-  const JpegOptBufs opt{hopt, hdrs, split};
-  JpegArgs a = jpeg_args(images, tables, header, coef, work, s420, restart, lj, false, &opt);
-  CHECK_DEV(out); CHECK_CONTIG(out);
-  TORCH_CHECK(out.scalar_type() == at::kByte && total > 0 && out.numel() == total, "jpeg: out uint8 [base[B]]");
-  a.out = out.data_ptr<uint8_t>();
-  launch_jpeg_write(a, cur_stream());
+// jpeg_encode_layout (jpeg_layout.h) for the callers that allocate; a refusal is a ValueError
+py::dict jpeg_encode_layout_dict(int64_t B, int64_t H, int64_t W, bool s420, int64_t restart, bool blocks, bool optimized,
+                                 bool lj, int64_t header_bytes) {
+  const JpegEncodeLayout l = jpeg_encode_layout(B, H, W, s420, restart, blocks, optimized, lj, header_bytes);
+  if (l.refusal != nullptr) throw py::value_error(l.refusal);
+  using namespace py::literals;
+  return py::dict("nb"_a = l.g.nb, "mx"_a = l.g.mx, "my"_a = l.g.my, "mcus"_a = l.g.mcus, "restart"_a = l.g.restart,
+                  "per"_a = l.g.per, "nint"_a = l.g.nint, "coef"_a = l.coef, "work"_a = l.work, "blk"_a = l.blk,
+                  "scratch"_a = l.scratch, "hopt"_a = l.hopt, "hdrs"_a = l.hdrs, "stride"_a = l.stride,
+                  "hdr_cap"_a = l.hdr_cap, "prefix"_a = l.prefix, "err"_a = l.err, "hdr_lens"_a = l.hdr_lens,
+                  "lens"_a = l.lens, "offs"_a = l.offs, "slack"_a = l.slack);
 }
 
 // The decoded pixels of the JPEG whose coefficients jpeg_count left in coef (decode contract:
@@ -1050,17 +986,14 @@ void jpeg_reconstruct(const at::Tensor& coef, const at::Tensor& tables, at::Tens
   TORCH_CHECK(H > 0 && W > 0 && H < 65536 && W < 65536, "jpeg: image sides must be in 1..65535");
   TORCH_CHECK(out.scalar_type() == at::kByte && out.dim() == 4 && out.size(0) > 0 && out.size(1) == H &&
               out.size(2) == W && out.size(3) == 3, "jpeg: out uint8 [B, H, W, 3]");
+  const JpegGeometry g = jpeg_geometry(H, W, s420 != 0, 0);
   JpegArgs a;
   a.B = (int)out.size(0); a.H = (int)H; a.W = (int)W;
-  const int mcu = s420 ? 16 : 8;
-  a.nb = s420 ? 6 : 3;
-  a.mx = (a.W + mcu - 1) / mcu; a.my = (a.H + mcu - 1) / mcu;
-  const long long mcus = (long long)a.B * a.mx * a.my;
-  TORCH_CHECK(coef.scalar_type() == at::kShort && coef.numel() == mcus * a.nb * 64,
-              "jpeg: coef int16 [B, mcus, blocks, 64]");
+  a.nb = g.nb; a.mx = g.mx; a.my = g.my;
+  const long long ncoef = a.B * g.mcus * g.nb * 64;
+  TORCH_CHECK(coef.scalar_type() == at::kShort && coef.numel() == ncoef, "jpeg: coef int16 [B, mcus, blocks, 64]");
   // every sample store of the idct kernel and every load of the colour kernel lands in planes
-  TORCH_CHECK(planes.scalar_type() == at::kByte && planes.numel() == mcus * a.nb * 64,
-              "jpeg: planes uint8 [B * mcus * blocks * 64]");
+  TORCH_CHECK(planes.scalar_type() == at::kByte && planes.numel() == ncoef, "jpeg: planes uint8 [B * mcus * blocks * 64]");
   TORCH_CHECK((double)a.B * a.H * ((a.W + 3) / 4) < 256.0 * 2147483647.0, "jpeg: batch too large for one launch");
   a.qtab = tables.data_ptr<int>();
   a.coef = coef.data_ptr<int16_t>();
@@ -1071,92 +1004,83 @@ void jpeg_reconstruct(const at::Tensor& coef, const at::Tensor& tables, at::Tens
   launch_jpeg_reconstruct(a, cur_stream());
 }
 
-// Entropy decode of B baseline streams of one geometry (entropy decode contract: jpeg.hip).
-// staged uint8 = the interval table (uint32 [B * intervals][2]: offset, length) followed by the
-// nbytes bytes the offsets index; tables int32 [672 + 1024] = the quantisation tables as
-// jpeg_reconstruct reads them (natural order, 128 of the 672 words used) | zig-zag quantisation
-// tables | four decode tables; buf int16 [B * mcus * blocks * 64 + 8]: the coefficients, then the
-// 64-bit status word (and 8 bytes of padding), all zeroed here.  restart 0: one interval.
-void jpeg_entropy_decode(const at::Tensor& staged, int64_t nbytes, const at::Tensor& tables, at::Tensor& buf,
-                         int64_t B, int64_t H, int64_t W, int64_t s420, int64_t restart) {
+// What the two entropy decodes of B baseline streams of one geometry share: the checks of staged,
+// tables and buf against jpeg_decode_layout (jpeg_layout.h), and the kernels' arguments.  staged
+// uint8 = the interval table (uint32 [B * intervals][2]: offset, length) followed by the nbytes
+// bytes the offsets index, and in chunked mode (extra >= 0) from byte `extra` on (a multiple of 4
+// at or behind the bytes) uint32 lane0 [B * intervals] and groups [ngroups][2]; tables int32
+// [672 + 1024] = the quantisation tables as jpeg_reconstruct reads them (natural order, 128 of the
+// 672 words used) | zig-zag quantisation tables | four decode tables; buf int16: the coefficients
+// and the status words behind them, all zeroed by the launch.  restart 0: one interval.
+struct JpegDecodeCall {
+  JpegArgs a;
+  JpegDecodeIn d;
+  JpegDecodeLayout l;
+};
+
+JpegDecodeCall jpeg_decode_args(const at::Tensor& staged, int64_t nbytes, const at::Tensor& tables, at::Tensor& buf,
+                                int64_t B, int64_t H, int64_t W, int64_t s420, int64_t restart, int64_t extra = -1,
+                                int64_t ngroups = 0) {
+  const bool chunked = extra >= 0;
   CHECK_DEV(staged); CHECK_CONTIG(staged); CHECK_DEV(tables); CHECK_CONTIG(tables); CHECK_DEV(buf); CHECK_CONTIG(buf);
-  TORCH_CHECK(B > 0 && H > 0 && W > 0 && H < 65536 && W < 65536, "jpeg: image sides must be in 1..65535");
-  TORCH_CHECK(restart >= 0 && restart < 65536, "jpeg: restart interval 0..65535");
+  JpegDecodeCall c;
+  const JpegDecodeLayout& l = c.l = jpeg_decode_layout(B, H, W, s420 != 0, restart, chunked);
+  TORCH_CHECK(l.refusal == nullptr, l.refusal);
   TORCH_CHECK(tables.scalar_type() == at::kInt && tables.numel() == 128 + 544 + 1024,
               "jpeg: decode tables int32 [672 + 1024]");
-  JpegArgs a;
-  a.B = (int)B; a.H = (int)H; a.W = (int)W;
-  const int mcu = s420 ? 16 : 8;
-  a.nb = s420 ? 6 : 3;
-  a.mx = (a.W + mcu - 1) / mcu; a.my = (a.H + mcu - 1) / mcu;
-  const long long mcus = (long long)a.mx * a.my;
-  a.restart = restart ? (int)restart : (int)mcus;
-  a.nint = (int)((mcus + a.restart - 1) / a.restart);
-  const long long nivals = B * a.nint, ncoef = B * mcus * a.nb * 64;
-  TORCH_CHECK(nivals < 2147483647LL, "jpeg: too many restart intervals for one launch");
-  TORCH_CHECK(buf.scalar_type() == at::kShort && buf.numel() == ncoef + 8, "jpeg: buf int16 [B * mcus * blocks * 64 + 8]");
-  TORCH_CHECK(nbytes >= 0 && nbytes < 4294967295LL && staged.scalar_type() == at::kByte &&
-              staged.numel() >= 8 * nivals + nbytes, "jpeg: staged uint8 [8 * B * intervals + nbytes]");
+  TORCH_CHECK(buf.scalar_type() == at::kShort && buf.numel() == l.buf,
+              chunked ? "jpeg: buf int16 [B * mcus * blocks * 64 + 16]" : "jpeg: buf int16 [B * mcus * blocks * 64 + 8]");
+  const bool bytes_ok = nbytes >= 0 && nbytes < 4294967295LL && staged.scalar_type() == at::kByte;
+  if (chunked) {
+    TORCH_CHECK(bytes_ok && extra % 4 == 0 && extra >= l.staged_min(nbytes) && staged.numel() >= extra + l.sync_bytes(ngroups),
+                "jpeg: staged uint8 [8 * B * intervals + nbytes | 4 * B * intervals + 8 * groups]");
+  } else {
+    TORCH_CHECK(bytes_ok && staged.numel() >= l.staged_min(nbytes), "jpeg: staged uint8 [8 * B * intervals + nbytes]");
+  }
   TORCH_CHECK(reinterpret_cast<uintptr_t>(staged.data_ptr()) % 4 == 0 && reinterpret_cast<uintptr_t>(buf.data_ptr()) % 16 == 0,
               "jpeg: staged 4-byte aligned, buf 16-byte aligned");
+  JpegArgs& a = c.a;
+  a.B = (int)B; a.H = (int)H; a.W = (int)W;
+  a.nb = l.g.nb; a.mx = l.g.mx; a.my = l.g.my;
+  a.restart = (int)l.g.restart;
+  a.nint = (int)l.g.nint;
   a.coef = buf.data_ptr<int16_t>();
-  JpegDecodeIn d;
+  JpegDecodeIn& d = c.d;
   d.intervals = reinterpret_cast<const uint32_t*>(staged.data_ptr<uint8_t>());
-  d.bytes = staged.data_ptr<uint8_t>() + 8 * nivals;
+  d.bytes = staged.data_ptr<uint8_t>() + 8 * l.nivals;
   d.nbytes = (uint32_t)nbytes;
   d.tables = reinterpret_cast<const uint32_t*>(tables.data_ptr<int>()) + 128 + 544;
-  d.status = reinterpret_cast<unsigned long long*>(a.coef + ncoef);     // 8-byte aligned: ncoef is a multiple of 64
-  d.zero_bytes = (ncoef + 8) * 2;
-  launch_jpeg_entropy_decode(a, d, cur_stream());
+  d.status = reinterpret_cast<unsigned long long*>(a.coef + l.ncoef);     // 8-byte aligned: ncoef is a multiple of 64
+  d.zero_bytes = l.buf * 2;
+  return c;
 }
 
-// The chunked entropy decode of the same inputs (chunked entropy decode contract: jpeg.hip).  staged
-// additionally holds, from byte `extra` on (a multiple of 4 at or behind the bytes), uint32
-// lane0 [B * intervals] and groups [ngroups][2]; buf int16 [B * mcus * blocks * 64 + 16]: the
-// coefficients, the status word (left 0 here), then uint32 flag, rounds, blocks completed, 0.
-// chunk = the effective chunk bytes, threads = lanes per workgroup.
+// Entropy decode, one lane per interval (entropy decode contract: jpeg.hip).  buf int16
+// [B * mcus * blocks * 64 + 8]: the coefficients, then the 64-bit status word (and 8 bytes of padding).
+void jpeg_entropy_decode(const at::Tensor& staged, int64_t nbytes, const at::Tensor& tables, at::Tensor& buf,
+                         int64_t B, int64_t H, int64_t W, int64_t s420, int64_t restart) {
+  const JpegDecodeCall c = jpeg_decode_args(staged, nbytes, tables, buf, B, H, W, s420, restart);
+  launch_jpeg_entropy_decode(c.a, c.d, cur_stream());
+}
+
+// The chunked entropy decode of the same inputs (chunked entropy decode contract: jpeg.hip).  buf
+// int16 [B * mcus * blocks * 64 + 16]: the coefficients, the status word (left 0 here), then uint32
+// flag, rounds, blocks completed, 0.  chunk = the effective chunk bytes, threads = lanes per workgroup.
 void jpeg_entropy_decode_chunked(const at::Tensor& staged, int64_t nbytes, const at::Tensor& tables, at::Tensor& buf,
                                  int64_t B, int64_t H, int64_t W, int64_t s420, int64_t restart, int64_t extra,
                                  int64_t ngroups, int64_t chunk, int64_t threads) {
-  CHECK_DEV(staged); CHECK_CONTIG(staged); CHECK_DEV(tables); CHECK_CONTIG(tables); CHECK_DEV(buf); CHECK_CONTIG(buf);
-  TORCH_CHECK(B > 0 && H > 0 && W > 0 && H < 65536 && W < 65536, "jpeg: image sides must be in 1..65535");
-  TORCH_CHECK(restart >= 0 && restart < 65536, "jpeg: restart interval 0..65535");
-  TORCH_CHECK(tables.scalar_type() == at::kInt && tables.numel() == 128 + 544 + 1024,
-              "jpeg: decode tables int32 [672 + 1024]");
-  JpegArgs a;
-  a.B = (int)B; a.H = (int)H; a.W = (int)W;
-  const int mcu = s420 ? 16 : 8;
-  a.nb = s420 ? 6 : 3;
-  a.mx = (a.W + mcu - 1) / mcu; a.my = (a.H + mcu - 1) / mcu;
-  const long long mcus = (long long)a.mx * a.my;
-  a.restart = restart ? (int)restart : (int)mcus;
-  a.nint = (int)((mcus + a.restart - 1) / a.restart);
-  const long long nivals = B * a.nint, ncoef = B * mcus * a.nb * 64;
-  TORCH_CHECK(nivals < 2147483647LL && ncoef / 64 < 256LL * 2147483647LL, "jpeg: too many restart intervals or blocks for one launch");
-  TORCH_CHECK(buf.scalar_type() == at::kShort && buf.numel() == ncoef + 16, "jpeg: buf int16 [B * mcus * blocks * 64 + 16]");
+  TORCH_CHECK(extra >= 0 && ngroups >= 0, "jpeg: staged uint8 [8 * B * intervals + nbytes | 4 * B * intervals + 8 * groups]");
+  const JpegDecodeCall c = jpeg_decode_args(staged, nbytes, tables, buf, B, H, W, s420, restart, extra, ngroups);
   TORCH_CHECK(chunk >= 16 && chunk % 16 == 0 && chunk < (1LL << 28), "jpeg: chunk bytes a multiple of 16");
   TORCH_CHECK(threads >= 64 && threads <= 1024 && threads % 64 == 0, "jpeg: 64..1024 lanes per workgroup");
-  TORCH_CHECK(ngroups >= 0 && ngroups <= nivals, "jpeg: at most one group per interval");
-  TORCH_CHECK(nbytes >= 0 && nbytes < 4294967295LL && staged.scalar_type() == at::kByte && extra % 4 == 0 &&
-              extra >= 8 * nivals + nbytes && staged.numel() >= extra + 4 * nivals + 8 * ngroups,
-              "jpeg: staged uint8 [8 * B * intervals + nbytes | 4 * B * intervals + 8 * groups]");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(staged.data_ptr()) % 4 == 0 && reinterpret_cast<uintptr_t>(buf.data_ptr()) % 16 == 0,
-              "jpeg: staged 4-byte aligned, buf 16-byte aligned");
-  a.coef = buf.data_ptr<int16_t>();
-  JpegDecodeIn d;
-  d.intervals = reinterpret_cast<const uint32_t*>(staged.data_ptr<uint8_t>());
-  d.bytes = staged.data_ptr<uint8_t>() + 8 * nivals;
-  d.nbytes = (uint32_t)nbytes;
-  d.tables = reinterpret_cast<const uint32_t*>(tables.data_ptr<int>()) + 128 + 544;
-  d.status = reinterpret_cast<unsigned long long*>(a.coef + ncoef);
-  d.zero_bytes = (ncoef + 16) * 2;
+  TORCH_CHECK(ngroups <= c.l.nivals, "jpeg: at most one group per interval");
   JpegSyncIn y;
   y.lane0 = reinterpret_cast<const uint32_t*>(staged.data_ptr<uint8_t>() + extra);
-  y.groups = y.lane0 + nivals;
+  y.groups = y.lane0 + c.l.nivals;
   y.ngroups = (int)ngroups;
   y.cb = (uint32_t)chunk;
-  y.words = reinterpret_cast<uint32_t*>(a.coef + ncoef + 4);
-  launch_jpeg_entropy_decode_chunked(a, d, y, (int)threads, cur_stream());
+  y.words = reinterpret_cast<uint32_t*>(c.a.coef + c.l.ncoef + 4);
+  launch_jpeg_entropy_decode_chunked(c.a, c.d, y, (int)threads, cur_stream());
 }
 
 // PIL's GaussianBlur (blur contract: blur_pil.hip).  img uint8 [H, W, 3]; out uint8 [N, H, W, 3].
@@ -1265,12 +1189,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("to_uint8", &to_uint8, nogil());
   m.def("jpeg_count", &jpeg_count, nogil());
   m.def("jpeg_write", &jpeg_write, nogil());
-  m.def("jpeg_count_blocks", &jpeg_count_blocks, nogil());
-  m.def("jpeg_write_blocks", &jpeg_write_blocks, nogil());
-  m.def("jpeg_count_opt", &jpeg_count_opt, nogil());
-  m.def("jpeg_write_opt", &jpeg_write_opt, nogil());
-  m.def("jpeg_count_blocks_opt", &jpeg_count_blocks_opt, nogil());
-  m.def("jpeg_write_blocks_opt", &jpeg_write_blocks_opt, nogil());
+  m.def("jpeg_encode_layout", &jpeg_encode_layout_dict);
   m.def("jpeg_reconstruct", &jpeg_reconstruct, nogil());
   m.def("jpeg_entropy_decode", &jpeg_entropy_decode, nogil());
   m.def("jpeg_entropy_decode_chunked", &jpeg_entropy_decode_chunked, nogil());

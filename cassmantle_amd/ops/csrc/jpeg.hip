@@ -1308,9 +1308,6 @@ __global__ __launch_bounds__(1024) void jpeg_blk_stuff_kernel(JpegArgs a, JpegBl
 
 }  // namespace
 
-int jpeg_blk_max_bits() { return (int)JPEG_BLK_MAX_BITS; }
-int jpeg_blk_max_bits_optimized() { return (int)JPEG_BLK_MAX_BITS_OPT; }
-
 // Optimised tables, behind the transform: zero freq, histogram, build (fills ihuff, hdrs, hdr_lens).
 static void launch_jpeg_huff_opt(const JpegArgs& a, hipStream_t s) {
   launch_zero(a.freq, (size_t)a.B * HUFF_WORDS * sizeof(uint32_t), s);

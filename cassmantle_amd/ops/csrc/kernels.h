@@ -257,8 +257,6 @@ struct JpegBlkArgs {
   uint32_t out_size = 0;             // launch_jpeg_write_blocks: payload bytes = base[B]; out[out_size] is raised
                                      // by a refused payload index
 };
-int jpeg_blk_max_bits();
-int jpeg_blk_max_bits_optimized();   // with optimised tables (a.ihuff): stride is sized with this
 // transform + bits per block + scan per interval + pack + 0xFF count per piece + the scans of
 // launch_jpeg_count: fills coef, bits, ubits, scratch, err, lens, offs, base
 void launch_jpeg_count_blocks(const JpegArgs& a, const JpegBlkArgs& k, hipStream_t s);

@@ -137,3 +137,59 @@ def test_serving_defaults_are_the_interval_coder():
     data, _ = build_content_jpeg_fn(cfg, DEV)(DeviceImage(x), 75)
     assert data == ops.jpeg_encode(x, 75, "420", row, entropy="interval")[0]
     assert jf.parse(data).restart == row
+
+
+@pytest.mark.parametrize("H,W", [(8, 8), (24, 40)])
+def test_bindings_take_the_layout_and_refuse_anything_else(H, W):
+    """ext().jpeg_count / jpeg_write directly, three images: with buffers sized by
+    ext().jpeg_encode_layout every coder / table combination writes the reference's bytes; a work
+    buffer one word short, half of an optional pair, a split without optimised tables and an out of
+    the wrong length are refused on the host, before anything is launched"""
+    from cassmantle_amd.ops._ext import ext
+    B, restart = 3, 2
+    batch = np.stack([jc.noise(H, W), jc.flat(H, W), jc.black_white_blocks(H, W)])
+    t = torch.from_numpy(batch).to(DEV)
+
+    def call(blocks, optimized):
+        tables, header, split = ops._jpeg_plan(t.device, H, W, 75, "420", restart, "compact", optimized)
+        lay = ext().jpeg_encode_layout(B, H, W, True, restart, blocks, optimized, False, header.numel())
+
+        def buf(name, dtype=torch.int32):
+            return torch.empty(lay[name], device=DEV, dtype=dtype)
+        blk, scratch = (buf("blk"), buf("scratch")) if blocks else (None, None)
+        hopt, hdrs = (buf("hopt"), buf("hdrs", torch.uint8)) if optimized else (None, None)
+        return lay, [t, tables, header, buf("coef", torch.int16), buf("work"), 1, restart, 0, blk, scratch, hopt, hdrs,
+                     split]
+
+    def replaced(args, **kw):
+        names = ["images", "tables", "header", "coef", "work", "s420", "restart", "lj", "blk", "scratch", "hopt", "hdrs",
+                 "split"]
+        return [kw.get(n, a) for n, a in zip(names, args)]
+
+    for blocks in (False, True):
+        for optimized in (False, True):
+            lay, args = call(blocks, optimized)
+            assert lay["lens"] == lay["prefix"] and lay["work"] == lay["prefix"] + 2 * B * lay["nint"]
+            with pytest.raises(RuntimeError):
+                ext().jpeg_count(*replaced(args, work=args[4][:-1]))
+            if blocks:
+                with pytest.raises(RuntimeError):
+                    ext().jpeg_count(*replaced(args, scratch=None))
+            if optimized:
+                with pytest.raises(RuntimeError):
+                    ext().jpeg_count(*replaced(args, hdrs=None))
+                with pytest.raises(RuntimeError):
+                    ext().jpeg_count(*replaced(args, hopt=None, hdrs=None))          # split stays
+            ext().jpeg_count(*args)
+            head = args[4][: lay["prefix"]].cpu().tolist()
+            total = head[B]
+            for wrong in (total + lay["slack"] - 1, total + lay["slack"] + 1):
+                with pytest.raises(RuntimeError):
+                    ext().jpeg_write(*args, torch.empty(wrong, device=DEV, dtype=torch.uint8), total)
+            out = torch.empty(total + lay["slack"], device=DEV, dtype=torch.uint8)
+            ext().jpeg_write(*args, out, total)
+            host = out.cpu().numpy().tobytes()
+            assert not (blocks and (head[lay["err"]] or host[-1]))
+            got = [host[head[i]: head[i + 1]] for i in range(B)]
+            exp = ref.jpeg_encode(batch, 75, "420", restart, huffman="optimized" if optimized else "standard")
+            assert got == exp, (blocks, optimized, [len(g) for g in got], [len(e) for e in exp])

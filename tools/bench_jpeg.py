@@ -118,80 +118,73 @@ def prewarm_once(blur_fn, blur_jpeg_fn, dimg, jpeg, tag):
     return n, wall, cpu, outs
 
 
-def encode_device_ms(batch, restart: int, iters: int = 5):
-    """Device time of the two launch groups of ops.jpeg_encode on ``batch`` (HIP events; nothing
-    else is queued): (transform + count + scans, write + headers) in ms."""
+def encode_layout(B: int, H: int, W: int, restart: int, block: bool = False, optimized: bool = False,
+                  transform: str = "matrix") -> dict:
+    """The buffer layout (ops/csrc/jpeg_layout.h) of an encode of this file's settings."""
+    from cassmantle_amd.ops import jpeg_format as jf
+    from cassmantle_amd.ops._ext import ext
+    lj, layout = transform == "libjpeg", jf.transform_layout(transform)
+    hdr = sum(len(p) for p in jf.header_parts(H, W, QUALITY, "420", restart, layout)) if optimized \
+        else len(jf.header(H, W, QUALITY, "420", restart, None, layout))
+    return ext().jpeg_encode_layout(B, H, W, True, restart, block, optimized, lj, hdr)
+
+
+def encode_args(batch, restart: int, block: bool = False, optimized: bool = False, transform: str = "matrix"):
+    """(layout, the arguments of ext().jpeg_count; jpeg_write takes out and the payload size behind
+    them) for ``batch``, buffers allocated as ops.jpeg_encode does."""
     import torch
     from cassmantle_amd import ops
     from cassmantle_amd.ops import jpeg_format as jf
-    from cassmantle_amd.ops._ext import ext
     B, H, W, _ = batch.shape
-    _, nb, mx, my = jf.geometry(H, W, "420")
-    nint = -(-mx * my // restart)
-    tables, header = ops._jpeg_plan(batch.device, H, W, QUALITY, "420", restart)
-    coef = torch.empty((B, mx * my, nb, 64), device="cuda", dtype=torch.int16)
-    work = torch.empty(2 * B * nint + B + 1, device="cuda", dtype=torch.int32)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    lay = encode_layout(B, H, W, restart, block, optimized, transform)
+    tables, header, split = ops._jpeg_plan(batch.device, H, W, QUALITY, "420", restart, jf.transform_layout(transform),
+                                           optimized)
+
+    def buf(name, dtype=torch.int32):
+        return torch.empty(lay[name], device="cuda", dtype=dtype)
+    blk, scratch = (buf("blk"), buf("scratch")) if block else (None, None)
+    hopt, hdrs = (buf("hopt"), buf("hdrs", torch.uint8)) if optimized else (None, None)
+    return lay, (batch, tables, header, buf("coef", torch.int16), buf("work"), 1, restart, int(transform == "libjpeg"),
+                 blk, scratch, hopt, hdrs, split)
+
+
+def encode_device_ms(batch, restart: int, iters: int = 5, block: bool = False):
+    """Device time of the two launch groups of ops.jpeg_encode on ``batch`` (HIP events; nothing
+    else is queued): (transform + count + scans, write + headers) in ms."""
+    import torch
+    from cassmantle_amd.ops._ext import ext
+    B = batch.shape[0]
+    lay, args = encode_args(batch, restart, block)
+    work = args[4]
     best = [1e9, 1e9]
     for _ in range(iters):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        torch.cuda.synchronize()
         ev[0].record()
-        ext().jpeg_count(batch, tables, header, coef, work, 1, restart, 0)
+        ext().jpeg_count(*args)
         ev[1].record()
         total = int(work[B].item())
-        out = torch.empty(total, device="cuda", dtype=torch.uint8)
+        out = torch.empty(total + lay["slack"], device="cuda", dtype=torch.uint8)
         torch.cuda.synchronize()
-        t0 = torch.cuda.Event(enable_timing=True)
-        t0.record()
-        ext().jpeg_write(batch, tables, header, coef, work, 1, restart, 0, out, total)
         ev[2].record()
+        ext().jpeg_write(*args, out, total)
+        ev[3].record()
         torch.cuda.synchronize()
-        best = [min(best[0], ev[0].elapsed_time(ev[1])), min(best[1], t0.elapsed_time(ev[2]))]
+        best = [min(best[0], ev[0].elapsed_time(ev[1])), min(best[1], ev[2].elapsed_time(ev[3]))]
     return best
 
 
 def block_buffers(B: int, H: int, W: int, restart: int):
     """(nint, stride, bytes allocated, bytes zeroed per call) of the block coder's device memory
     beyond coefficients and payload; ``restart`` 0 = no restart markers."""
-    from cassmantle_amd.ops import jpeg_format as jf
-    _, nb, mx, my = jf.geometry(H, W, "420")
-    per = min(restart, mx * my) if restart else mx * my
-    nint = -(-mx * my // per)
-    stride = (per * nb * jf.block_bits_bound() + 31) // 32
-    nblk = B * mx * my * nb
-    return nint, stride, 4 * (B * nint * stride + nblk + B * nint + 1), 4 * (nblk + B * nint) + 4 + 1
+    lay = encode_layout(B, H, W, restart, block=True)
+    return lay["nint"], lay["stride"], 4 * (lay["scratch"] + lay["blk"] + 1), 4 * lay["blk"] + 4 + 1
 
 
 def encode_blocks_device_ms(batch, restart: int, iters: int = 5):
     """encode_device_ms for ``entropy="block"`` (``restart`` 0 = no restart markers): (transform +
     bits + scan + pack + piece counts + scans, stuffed write + headers) in ms."""
-    import torch
-    from cassmantle_amd import ops
-    from cassmantle_amd.ops import jpeg_format as jf
-    from cassmantle_amd.ops._ext import ext
-    B, H, W, _ = batch.shape
-    _, nb, mx, my = jf.geometry(H, W, "420")
-    nint, stride, _, _ = block_buffers(B, H, W, restart)
-    tables, header = ops._jpeg_plan(batch.device, H, W, QUALITY, "420", restart)
-    coef = torch.empty((B, mx * my, nb, 64), device="cuda", dtype=torch.int16)
-    work = torch.empty(2 * B * nint + B + 2, device="cuda", dtype=torch.int32)
-    blk = torch.empty(B * mx * my * nb + B * nint, device="cuda", dtype=torch.int32)
-    scratch = torch.empty(B * nint * stride, device="cuda", dtype=torch.int32)
-    best = [1e9, 1e9]
-    for _ in range(iters):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        torch.cuda.synchronize()
-        ev[0].record()
-        ext().jpeg_count_blocks(batch, tables, header, coef, work, blk, scratch, stride, 1, restart, 0)
-        ev[1].record()
-        total = int(work[B].item())
-        out = torch.empty(total + 1, device="cuda", dtype=torch.uint8)
-        torch.cuda.synchronize()
-        ev[2].record()
-        ext().jpeg_write_blocks(batch, tables, header, coef, work, blk, scratch, stride, 1, restart, 0, out, total)
-        ev[3].record()
-        torch.cuda.synchronize()
-        best = [min(best[0], ev[0].elapsed_time(ev[1])), min(best[1], ev[2].elapsed_time(ev[3]))]
-    return best
+    return encode_device_ms(batch, restart, iters, block=True)
 
 
 def block_main(a, emit) -> int:
@@ -285,7 +278,7 @@ def block_main(a, emit) -> int:
                 rec.update(scratch_bytes_allocated=alloc, scratch_bytes_zeroed=zeroed)
             else:
                 cnt, wr = encode_device_ms(pixels, restart)
-                nint = -(-((res + 15) // 16) ** 2 // restart)
+                nint = encode_layout(pixels.shape[0], res, res, restart)["nint"]
                 rec.update(scratch_bytes_allocated=8 * pixels.shape[0] * nint, scratch_bytes_zeroed=0)
             emit(dict(rec, count_phase_device_ms=round(cnt, 4), write_phase_device_ms=round(wr, 4)))
     return 0
@@ -297,41 +290,14 @@ def count_phase_device_ms(batch, restart: int, entropy: str, optimized: bool, it
     ``batch``: transform (+ histogram + table build with ``optimized``) + the coder's count pass +
     scans, in ms; ``restart`` 0 = no restart markers (block coder)."""
     import torch
-    from cassmantle_amd import ops
-    from cassmantle_amd.ops import jpeg_format as jf
     from cassmantle_amd.ops._ext import ext
-    B, H, W, _ = batch.shape
-    _, nb, mx, my = jf.geometry(H, W, "420")
-    per = min(restart, mx * my) if restart else mx * my
-    nint = -(-mx * my // per)
-    opt, sfx = (), ""
-    lj, layout = int(transform == "libjpeg"), jf.transform_layout(transform)
-    if optimized:
-        tables, header, split = ops._jpeg_opt_plan(batch.device, H, W, QUALITY, "420", restart, layout)
-        dht_cap = 4 + (jf.DHT_EXTRA_PIL if lj else 0) + 4 * (17 + 256)
-        opt = (torch.empty(2 * B * 544, device="cuda", dtype=torch.int32),
-               torch.empty(B * (header.numel() + dht_cap), device="cuda", dtype=torch.uint8), split)
-        sfx = "_opt"
-    else:
-        tables, header = ops._jpeg_plan(batch.device, H, W, QUALITY, "420", restart, layout)
-    coef = torch.empty((B, mx * my, nb, 64), device="cuda", dtype=torch.int16)
-    block = entropy == "block"
-    work = torch.empty(2 * B * nint + B + 1 + int(block) + (B if optimized else 0), device="cuda", dtype=torch.int32)
-    if block:
-        bound = jf.block_bits_bound_optimized() if optimized else jf.block_bits_bound()
-        stride = (per * nb * bound + 31) // 32
-        blk = torch.empty(B * mx * my * nb + B * nint, device="cuda", dtype=torch.int32)
-        scratch = torch.empty(B * nint * stride, device="cuda", dtype=torch.int32)
+    _, args = encode_args(batch, restart, entropy == "block", optimized, transform)
     best = 1e9
     for _ in range(iters):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
         e0.record()
-        if block:
-            getattr(ext(), "jpeg_count_blocks" + sfx)(batch, tables, header, coef, work, blk, scratch, stride, 1, restart, lj,
-                                                      *opt)
-        else:
-            getattr(ext(), "jpeg_count" + sfx)(batch, tables, header, coef, work, 1, restart, lj, *opt)
+        ext().jpeg_count(*args)
         e1.record()
         torch.cuda.synchronize()
         best = min(best, e0.elapsed_time(e1))
@@ -475,16 +441,11 @@ def reconstruct_device_ms(t, restart: int, iters: int = 5) -> float:
     """Device time of the idct + colour kernels behind ``return_decoded`` for the [1, H, W, 3]
     image ``t`` (HIP events around the two launches; nothing else is queued), in ms."""
     import torch
-    from cassmantle_amd import ops
-    from cassmantle_amd.ops import jpeg_format as jf
     from cassmantle_amd.ops._ext import ext
     B, H, W, _ = t.shape
-    _, nb, mx, my = jf.geometry(H, W, "420")
-    nint = -(-mx * my // restart)
-    tables, header = ops._jpeg_plan(t.device, H, W, QUALITY, "420", restart)
-    coef = torch.empty((B, mx * my, nb, 64), device="cuda", dtype=torch.int16)
-    work = torch.empty(2 * B * nint + B + 1, device="cuda", dtype=torch.int32)
-    ext().jpeg_count(t, tables, header, coef, work, 1, restart, 0)
+    _, args = encode_args(t, restart)
+    tables, coef = args[1], args[3]
+    ext().jpeg_count(*args)
     planes = torch.empty(coef.numel(), device="cuda", dtype=torch.uint8)
     out = torch.empty((B, H, W, 3), device="cuda", dtype=torch.uint8)
     best = 1e9
@@ -654,7 +615,7 @@ def decode_main(a, emit) -> int:
     def entropy_device_ms(stream, iters: int = 5):
         """(zero + entropy decode launch, zero alone) device time in ms, HIP events, nothing else queued"""
         _, nb, mx, my = jf.geometry(stream.H, stream.W, stream.sampling)
-        staged, base, tables = ops._jpeg_decode_inputs([stream], torch.device("cuda"))
+        staged, base, tables, _ = ops._jpeg_decode_inputs([stream], torch.device("cuda"))
         buf = torch.empty(mx * my * nb * 64 + 8, device="cuda", dtype=torch.int16)
         best = [1e9, 1e9]
         for _ in range(iters + 1):
