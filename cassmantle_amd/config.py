@@ -112,7 +112,11 @@ class ModelConfig:
     resolution: int = 512
     steps: int = 50
     guidance_scale: float = 7.5
-    scheduler: str = "pndm"               # pndm | ddim | euler
+    # pndm | ddim | euler | euler_a | dpmpp_2m | dpmpp_2m_karras | dpmpp_2m_sde | dpmpp_2m_sde_karras
+    # (models/schedulers.py; DPM-Solver++ 2M is meant for 20-25 steps; euler_a and the *_sde ones
+    # draw fresh noise every step, reproducible from the image's seed); an unknown name is refused
+    # when the generator is built (runtime/factory.py)
+    scheduler: str = "pndm"
     # rooms that share one device pipeline have their concurrent generation requests batched
     # into one denoise loop (game/content.BatchingImageGenerator): up to gen_batch_max images,
     # collected for gen_batch_window_ms

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import math
 import os
+import weakref
 from typing import List, Optional
 
 import torch
@@ -1245,24 +1246,54 @@ def finalize_latents(x: torch.Tensor, z: torch.Tensor, finite: torch.Tensor) -> 
     ext().finalize_latents(x, z, finite)
 
 
+# coefficient tables known to the latent step: id(table) -> (weak reference, version, has a
+# non-zero noise column).  Looked up only when a table comes without seeds, to refuse a stochastic
+# table there; one device read per table (and per in-place change of it), never inside a capture.
+_NOISE_TABLES: dict = {}
+
+
+def declare_latent_table(coef: torch.Tensor, draws_noise: bool) -> torch.Tensor:
+    """Tell the latent step what the host already knows of a device table (the pipeline builds it
+    from a plan): no device read for it later."""
+    key = id(coef)
+    _NOISE_TABLES[key] = (weakref.ref(coef, lambda _, k=key: _NOISE_TABLES.pop(k, None)), coef._version,
+                          bool(draws_noise))
+    return coef
+
+
+def _table_draws_noise(coef: torch.Tensor) -> bool:
+    hit = _NOISE_TABLES.get(id(coef))
+    if hit is not None and hit[0]() is coef and hit[1] == coef._version:
+        return hit[2]
+    if torch.cuda.is_current_stream_capturing():
+        return False
+    flag = bool((coef[:, 15] != 0).any().item())
+    declare_latent_table(coef, flag)
+    return flag
+
+
 def latent_step(eps: torch.Tensor, x: torch.Tensor, hist: torch.Tensor, xs: torch.Tensor,
                 coef: torch.Tensor, step: torch.Tensor, unet_in: torch.Tensor, cfg: bool,
-                rows=None) -> None:
+                rows=None, noise_seeds: Optional[torch.Tensor] = None) -> None:
     """Fused CFG-combine + scheduler update + next-step UNet-input write (see
     ``models/schedulers.py`` for the coefficient-table contract).  In place on x/hist/xs/unet_in;
     ``unet_in`` may be channel-padded (its extra channels stay zero).  ``rows``: up to two
     ``(table [E, ...], buffer)`` pairs — row ``min(step + 1, E - 1)`` of each table is copied into
     its buffer by the same launch (the next step's time conditioning).  ``step`` is a device
-    int32 scalar so the whole step is graph-capturable."""
+    int32 scalar so the whole step is graph-capturable.  ``noise_seeds``: int64 ``[B]`` device
+    tensor, one seed per image, for a table with stochastic rows (column 15: Gaussian noise drawn
+    in the kernel by the noise contract of ``models/schedulers.py``); such a table without seeds
+    is an error."""
     rows = list(rows or [])
     if not _use_hip(x):
         from ..models.schedulers import latent_step_reference
-        latent_step_reference(eps, x, hist, xs, coef, step, unet_in, cfg)
+        latent_step_reference(eps, x, hist, xs, coef, step, unet_in, cfg, noise_seeds=noise_seeds)
         for tab, buf in rows:
             buf.copy_(tab[min(int(step.item()) + 1, tab.shape[0] - 1)].view_as(buf))
         return
     (t0, b0), (t1, b1) = (rows + [(None, None), (None, None)])[:2]
-    ext().latent_step(eps, x, hist, xs, coef, step, unet_in, int(cfg), t0, b0, t1, b1)
+    ext().latent_step(eps, x, hist, xs, coef, step, unet_in, int(cfg), t0, b0, t1, b1, noise_seeds,
+                      noise_seeds is None and _table_draws_noise(coef))
 
 
 def copy_(dst: torch.Tensor, src: torch.Tensor) -> torch.Tensor:

@@ -699,7 +699,8 @@ void finalize_latents(const at::Tensor& x, at::Tensor& z, at::Tensor& finite) {
 void latent_step(const at::Tensor& eps, at::Tensor& x, at::Tensor& hist, at::Tensor& xs, const at::Tensor& coef,
                  const at::Tensor& step, at::Tensor& unet_in, int64_t cfg, const c10::optional<at::Tensor>& tab0,
                  const c10::optional<at::Tensor>& buf0, const c10::optional<at::Tensor>& tab1,
-                 const c10::optional<at::Tensor>& buf1) {
+                 const c10::optional<at::Tensor>& buf1, const c10::optional<at::Tensor>& noise_seeds,
+                 bool noise_rows) {
   CHECK_DEV(x); CHECK_BF16(eps); CHECK_CONTIG(eps); CHECK_BF16(unet_in); CHECK_CONTIG(unet_in);
   TORCH_CHECK(x.scalar_type() == at::kFloat && hist.scalar_type() == at::kFloat && xs.scalar_type() == at::kFloat,
               "latent_step: f32 master latents");
@@ -718,12 +719,31 @@ void latent_step(const at::Tensor& eps, at::Tensor& x, at::Tensor& hist, at::Ten
   const bool h0 = tab_ok(tab0, buf0), h1 = tab_ok(tab1, buf1);
   const int rows = h0 ? (int)tab0->size(0) : (h1 ? (int)tab1->size(0) : 0);
   TORCH_CHECK(!(h0 && h1) || tab1->size(0) == rows, "latent_step: tables of equal row count");
+  // noise_rows: the caller's knowledge that the table has a non-zero column 15 (stochastic rows)
+  const bool seeded = noise_seeds.has_value() && noise_seeds->defined();
+  TORCH_CHECK(seeded || !noise_rows, "latent_step: the table has stochastic rows (column 15) but no noise_seeds");
+  const void* seeds = nullptr;
+  int images = 0;
+  if (seeded) {
+    const at::Tensor& sd = *noise_seeds;
+    CHECK_DEV(sd); CHECK_CONTIG(sd); CHECK_CONTIG(x); CHECK_CONTIG(xs); CHECK_CONTIG(hist);
+    TORCH_CHECK(sd.scalar_type() == at::kLong && sd.dim() == 1 && sd.numel() >= 1 && sd.numel() == x.size(0) &&
+                sd.numel() < (1ll << 31), "latent_step: noise_seeds is int64 [B], one seed per image of x");
+    TORCH_CHECK(cin == 4 && n % (4 * sd.numel()) == 0 && n / (4 * sd.numel()) <= (1ll << 32),
+                "latent_step: noise needs 4-channel latents of at most 2^32 pixels per image");
+    auto al = [](const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; };
+    TORCH_CHECK(al(x.data_ptr(), 16) && al(xs.data_ptr(), 16) && al(hist.data_ptr(), 16) && al(eps.data_ptr(), 8) &&
+                al(unet_in.data_ptr(), 8) && al(sd.data_ptr(), 8) && cstride % 4 == 0,
+                "latent_step: noise path needs 16-byte aligned latents, 8-byte aligned eps / unet_in");
+    seeds = sd.data_ptr();
+    images = (int)sd.numel();
+  }
   launch_latent_step(bptr(eps), x.data_ptr<float>(), hist.data_ptr<float>(), xs.data_ptr<float>(),
                      coef.data_ptr<float>(), step.data_ptr<int>(), bptr_mut(unet_in), n, (int)cfg, cin, cstride,
                      h0 ? tab0->data_ptr() : nullptr, h0 ? buf0->data_ptr() : nullptr,
                      h0 ? buf0->numel() * buf0->element_size() : 0, h1 ? tab1->data_ptr() : nullptr,
                      h1 ? buf1->data_ptr() : nullptr, h1 ? buf1->numel() * buf1->element_size() : 0, rows,
-                     cur_stream());
+                     seeds, images, cur_stream());
 }
 
 // A HIP stream whose kernels may only run on the CUs of ``mask`` (bit i of word i / 32 = CU i):

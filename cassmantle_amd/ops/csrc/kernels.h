@@ -200,11 +200,13 @@ void launch_latent_init(const float* x0, float c_in0, float* x, float* xs, float
 void launch_copy(const void* src, void* dst, long long bytes, hipStream_t s);
 void launch_finalize_latents(const float* x, uint16_t* z, long long n, uint8_t* finite, hipStream_t s);
 // CFG combine + scheduler update + next UNet input (channel-padded to cstride); the optional
-// tables' rows for step+1 (time conditioning) are copied into buf0/buf1 by extra blocks
+// tables' rows for step+1 (time conditioning) are copied into buf0/buf1 by extra blocks.
+// ``seeds`` (nullptr: a deterministic plan, row column 15 ignored): one 64-bit noise seed per
+// image, ``images`` of them; then cin == 4 and 16-byte aligned latents (philox_normal.h)
 void launch_latent_step(const uint16_t* eps, float* x, float* hist, float* xs, const float* coef, const int* step,
                         uint16_t* unet_in, long long n, int cfg, int cin, int cstride, const void* tab0, void* buf0,
                         long long row_bytes0, const void* tab1, void* buf1, long long row_bytes1, int rows,
-                        hipStream_t s);
+                        const void* seeds, int images, hipStream_t s);
 void launch_advance_step(int* step, hipStream_t s);
 void launch_zero(void* p, long long bytes, hipStream_t s);
 void launch_prefetch(const void* p, long long bytes, int blocks, void* sink, hipStream_t s);

@@ -13,9 +13,12 @@
 // * to_uint8 (K18): VAE output [-1, 1] -> uint8 (x/2 + 0.5 clamp, *255, round).
 // * timestep_embedding (K10), latent_step (K11: CFG combine + scheduler update + next UNet
 //   input, reading its coefficient row through a device step counter so a hipGraph replays
-//   it unchanged), advance_step, softmax_rows (VAE d=512 attention path).
+//   it unchanged; latent_step_noise_kernel for plans with stochastic rows: one lane per latent
+//   pixel, Gaussian noise from philox_normal.h keyed by the image's seed, the eval and the pixel),
+//   advance_step, softmax_rows (VAE d=512 attention path).
 #include "common.h"
 #include "kernels.h"
+#include "philox_normal.h"
 
 namespace {
 
@@ -305,6 +308,79 @@ __global__ void latent_step_kernel(const uint16_t* __restrict__ eps, float* __re
   const long long un = (n / cin) * cstride;
   unet_in[ui] = o;
   if (cfg) unet_in[un + ui] = o;
+}
+
+// latent_step for plans with stochastic rows (row column 15, ``noise``):
+//     x = ax x + axs XS + b e' + r[15] z,   z ~ N(0, 1) by the NOISE CONTRACT of philox_normal.h
+// One lane per latent pixel (cin == 4): its four channels are one 16-byte access of every fp32
+// buffer and ONE Philox call.  r[15] != 0 is uniform over the launch (the row comes from the step
+// counter), so a deterministic row of such a plan (its last) runs no Philox and reads no seed.
+// ``seeds``: one 64-bit seed per image as (low, high) words; ``ppi``: pixels per image.
+__global__ void latent_step_noise_kernel(const uint16_t* __restrict__ eps, float* __restrict__ x,
+                                         float* __restrict__ hist, float* __restrict__ xs,
+                                         const float* __restrict__ coef, const int* __restrict__ step,
+                                         uint16_t* __restrict__ unet_in, long long npix, long long ppi, int cfg,
+                                         int cstride, const uint2* __restrict__ seeds, int latent_blocks,
+                                         StepRows rows) {
+  if ((int)blockIdx.x >= latent_blocks) {                   // next step's conditioning rows, as above
+    const int s = min(step[0] + 1, rows.rows - 1);
+    const long long b = (long long)(blockIdx.x - latent_blocks) * blockDim.x + threadIdx.x;
+    const long long tot0 = rows.row_units[0];
+    if (b < tot0) {
+      rows.buf[0][b] = rows.tab[0][(long long)s * tot0 + b];
+    } else if (b - tot0 < rows.row_units[1]) {
+      rows.buf[1][b - tot0] = rows.tab[1][(long long)s * rows.row_units[1] + (b - tot0)];
+    }
+    return;
+  }
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= npix) return;
+  const int st = step[0];
+  const float* r = coef + 16 * st;
+  const uint2 pu = reinterpret_cast<const uint2*>(eps)[i];
+  float e[4] = {__uint_as_float(pu.x << 16), __uint_as_float(pu.x & 0xffff0000u), __uint_as_float(pu.y << 16),
+                __uint_as_float(pu.y & 0xffff0000u)};
+  if (cfg) {
+    const uint2 pc = reinterpret_cast<const uint2*>(eps)[npix + i];
+    const float c[4] = {__uint_as_float(pc.x << 16), __uint_as_float(pc.x & 0xffff0000u),
+                        __uint_as_float(pc.y << 16), __uint_as_float(pc.y & 0xffff0000u)};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) e[k] = e[k] + r[13] * (c[k] - e[k]);
+  }
+  float ep[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) ep[k] = r[0] * e[k];
+  float4* h4 = reinterpret_cast<float4*>(hist);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int sj = (int)r[8 + j];
+    if (sj >= 0) {
+      const float4 h = h4[(long long)sj * npix + i];
+      ep[0] = fmaf(r[1 + j], h.x, ep[0]); ep[1] = fmaf(r[1 + j], h.y, ep[1]);
+      ep[2] = fmaf(r[1 + j], h.z, ep[2]); ep[3] = fmaf(r[1 + j], h.w, ep[3]);
+    }
+  }
+  const float4 xo = reinterpret_cast<float4*>(x)[i];
+  const float4 xv = reinterpret_cast<float4*>(xs)[i];
+  float xn[4] = {r[4] * xo.x + r[5] * xv.x + r[6] * ep[0], r[4] * xo.y + r[5] * xv.y + r[6] * ep[1],
+                 r[4] * xo.z + r[5] * xv.z + r[6] * ep[2], r[4] * xo.w + r[5] * xv.w + r[6] * ep[3]};
+  if (r[15] != 0.f) {
+    const long long b = i / ppi;
+    const uint2 seed = seeds[b];
+    uint32_t w[4];
+    float z[4];
+    philox_normal4(seed.x, seed.y, (uint32_t)(i - b * ppi), (uint32_t)st, w, z);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) xn[k] = fmaf(r[15], z[k], xn[k]);
+  }
+  const int sv = (int)r[11];
+  if (sv >= 0) h4[(long long)sv * npix + i] = make_float4(e[0], e[1], e[2], e[3]);
+  if (r[12] > 0.f) reinterpret_cast<float4*>(xs)[i] = xo;
+  reinterpret_cast<float4*>(x)[i] = make_float4(xn[0], xn[1], xn[2], xn[3]);
+  // (channel-padded UNet input as in latent_step_kernel: channels 0..3 of a pixel of cstride)
+  const uint2 o = make_uint2(pack2(r[7] * xn[0], r[7] * xn[1]), pack2(r[7] * xn[2], r[7] * xn[3]));
+  *reinterpret_cast<uint2*>(unet_in + i * cstride) = o;
+  if (cfg) *reinterpret_cast<uint2*>(unet_in + (npix + i) * cstride) = o;
 }
 
 __global__ void advance_step_kernel(int* step) { step[0] += 1; }
@@ -662,15 +738,22 @@ void launch_finalize_latents(const float* x, uint16_t* z, long long n, uint8_t* 
 void launch_latent_step(const uint16_t* eps, float* x, float* hist, float* xs, const float* coef, const int* step,
                         uint16_t* unet_in, long long n, int cfg, int cin, int cstride, const void* tab0, void* buf0,
                         long long row_bytes0, const void* tab1, void* buf1, long long row_bytes1, int rows,
-                        hipStream_t s) {
+                        const void* seeds, int images, hipStream_t s) {
   StepRows r;
   r.tab[0] = reinterpret_cast<const uint4*>(tab0); r.buf[0] = reinterpret_cast<uint4*>(buf0);
   r.tab[1] = reinterpret_cast<const uint4*>(tab1); r.buf[1] = reinterpret_cast<uint4*>(buf1);
   r.row_units[0] = tab0 ? (int)(row_bytes0 / 16) : 0;
   r.row_units[1] = tab1 ? (int)(row_bytes1 / 16) : 0;
   r.rows = rows;
-  const int lb = (int)nblk(n, 256);
   const int cb = (int)nblk((long long)r.row_units[0] + r.row_units[1], 256);
+  if (seeds != nullptr) {           // a plan with stochastic rows: one lane per pixel (cin == 4)
+    const long long npix = n / 4;
+    const int lb = (int)nblk(npix, 256);
+    hipLaunchKernelGGL(latent_step_noise_kernel, dim3(lb + cb), dim3(256), 0, s, eps, x, hist, xs, coef, step,
+                       unet_in, npix, npix / images, cfg, cstride, reinterpret_cast<const uint2*>(seeds), lb, r);
+    return;
+  }
+  const int lb = (int)nblk(n, 256);
   hipLaunchKernelGGL(latent_step_kernel, dim3(lb + cb), dim3(256), 0, s, eps, x, hist, xs, coef, step, unet_in, n,
                      cfg, cin, cstride, lb, r);
 }

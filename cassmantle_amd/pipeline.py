@@ -26,7 +26,7 @@ import torch
 
 from . import ops
 from .game.content import ImageGenerator, ImageGenerationError
-from .models.schedulers import SchedulePlan, make_plan
+from .models.schedulers import SchedulePlan, check_scheduler, make_plan, seeds_int64
 from .models.text import CLIP_BIGG, CLIP_L, TINY_CLIP, CLIPTextEncoder, CLIPTextConfig
 from .models.unet import SD15_UNET, SDXL_UNET, TINY_UNET, UNet, UNetConfig
 from .models.vae import SD_VAE, SDXL_VAE, TINY_VAE, VAEConfig, VAEDecoder
@@ -84,7 +84,11 @@ class _StepState:
         self.unet_in = ops.zero_(torch.empty((nb, h, w, 8 if torch.device(device).type == "cuda" else 4),
                                              device=device, dtype=dtype))
         self.ctx = torch.empty_like(ctx)
-        self.coef = torch.from_numpy(plan.table).to(device)
+        self.coef = ops.declare_latent_table(torch.from_numpy(plan.table).to(device), plan.stochastic)
+        # one 64-bit noise seed per image for a plan with stochastic rows (read by the captured
+        # latent step: the noise contract of models/schedulers.py), refilled by load()
+        self.noise_seeds = (ops.zero_(torch.empty((B,), device=device, dtype=torch.int64))
+                            if plan.stochastic else None)
         self.tsteps = torch.from_numpy(plan.table[:, 14].copy()).to(device)
         # the time table's per-row inputs, built on the host once per state: t of row e*nb + b
         # and the row -> image index of the add-embedding repeat (no device repeat kernels)
@@ -120,9 +124,13 @@ class _StepState:
             ops.copy_(self.temb_tab, temb)
             ops.copy_(self.tb_tab, tb)
 
-    def load(self, x0: torch.Tensor, ctx: torch.Tensor, added: Optional[dict]):
+    def load(self, x0: torch.Tensor, ctx: torch.Tensor, added: Optional[dict], seeds: Optional[Sequence[int]] = None):
         # x, xs, hist and the first UNet input (both CFG halves) in one kernel
         ops.latent_init(x0, self.plan.c_in0, self.x, self.xs, self.hist, self.unet_in, self.cfg)
+        if self.noise_seeds is not None:
+            if seeds is None or len(seeds) != self.B:
+                raise ValueError(f"scheduler {self.plan.name} draws noise: it needs one seed per image")
+            ops.copy_(self.noise_seeds, ops.h2d(torch.from_numpy(seeds_int64(seeds)), self.noise_seeds.device))
         # (in-tree copy kernels: no runtime blit in a generation's trace)
         ops.copy_(self.ctx, ctx)
         if self.temb_tab is not None:
@@ -204,7 +212,7 @@ class StableDiffusion:
         # then by the previous step's latent-step launch from the device step counter)
         eps = self.unet(st.unet_in, None, st.ctx, st.added, fp8=self.fp8, time_cond=(st.temb_cur, st.tb_cur))
         ops.latent_step(eps, st.x, st.hist, st.xs, st.coef, st.step, st.unet_in, st.cfg,
-                        rows=[(st.temb_tab, st.temb_cur), (st.tb_tab, st.tb_cur)])
+                        rows=[(st.temb_tab, st.temb_cur), (st.tb_tab, st.tb_cur)], noise_seeds=st.noise_seeds)
         ops.advance_step(st.step)
 
     def prepare(self) -> None:
@@ -265,7 +273,8 @@ class StableDiffusion:
 
     @torch.no_grad()
     def denoise(self, ctx: torch.Tensor, latents: torch.Tensor, plan: SchedulePlan,
-                added: Optional[dict] = None) -> torch.Tensor:
+                added: Optional[dict] = None, seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """``seeds``: the images' seeds (those of ``init_latents``), needed by a plan that draws noise."""
         B = latents.shape[0]
         st = self._state(B, ctx, plan, added)
         self._last_state = st
@@ -278,9 +287,9 @@ class StableDiffusion:
         st.load_time(*self.unet.time_table(st.tsteps, st.unet_in.shape[0], added_t, t_rep=st.t_rep,
                                            rep_ids=st.rep_ids))
         if self.use_graphs and st.graph is None:
-            st.load(latents, ctx, added)
+            st.load(latents, ctx, added, seeds)
             self._capture(st)
-        st.load(latents, ctx, added)
+        st.load(latents, ctx, added, seeds)
         for _ in range(plan.evals):
             if st.graph is not None:
                 st.graph.replay()
@@ -328,7 +337,7 @@ class StableDiffusion:
                 ctx, added = self.encode_prompt(prompts, negative)
                 x0 = self.init_latents(seeds, plan)
             with span("denoise", self.stream):
-                x = self.denoise(ctx, x0, plan, added)
+                x = self.denoise(ctx, x0, plan, added, seeds)
             # bf16 latents for the VAE + finiteness flag of the fp32 latents, one kernel (the
             # flag is checked before the uint8 decode, where NaN/Inf would silently become a
             # garbage image)
@@ -399,6 +408,8 @@ class DiffusionImageGenerator(ImageGenerator):
                  guidance: Optional[float] = None, scheduler: Optional[str] = None,
                  use_graphs: bool = True, fp8_attention: bool = False, seed: int = 0,
                  dtype=torch.bfloat16, weights_path: Optional[str] = None, stream=None) -> None:
+        # (a bad scheduler name fails here, when the generator is built, not at the first round)
+        scheduler = check_scheduler(scheduler) if scheduler is not None else None
         self.sd = StableDiffusion(SPECS[model], device=device, use_graphs=use_graphs,
                                   fp8_attention=fp8_attention, seed=seed, dtype=dtype, stream=stream)
         self.weights_loaded: Optional[Dict[str, int]] = None

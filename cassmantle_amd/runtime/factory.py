@@ -293,6 +293,8 @@ def build_prompt_generator(cfg: Config, device: Optional[str] = None):
 
 def build_image_generator(cfg: Config, device: Optional[str] = None) -> ImageGenerator:
     m = cfg.model
+    from ..models.schedulers import check_scheduler
+    check_scheduler(m.scheduler)            # a bad ModelConfig.scheduler raises here, not at the first round
     use_gpu = (m.device == "cuda") or (m.device == "auto" and torch.cuda.is_available())
     if m.image_model == "remote":
         if not m.remote_image_url:
