@@ -115,7 +115,9 @@ void gemm(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tens
   TORCH_CHECK(w.size(1) == p.K, "gemm: K mismatch");
   TORCH_CHECK(out.size(0) == p.M, "gemm: M mismatch");
   if (act == 4 || act == 6) {
-    TORCH_CHECK(p.Nw == 2 * p.N && p.K % 8 == 0 && p.N % 4 == 0, "geglu/swiglu: W must be [2N,K], K%8==0, N%4==0");
+    // (the GEMV that takes <= 8 rows owns whole columns: any N; the MFMA gated tiles pair 4 columns)
+    TORCH_CHECK(p.Nw == 2 * p.N && p.K % 8 == 0 && (p.N % 4 == 0 || (p.M >= 1 && p.M <= 8 && p.lda % 8 == 0)),
+                "geglu/swiglu: W must be [2N,K], K%8==0, N%4==0 (any N for <= 8 rows with lda%8==0)");
   } else {
     TORCH_CHECK(p.Nw == p.N, "gemm: N mismatch");
   }

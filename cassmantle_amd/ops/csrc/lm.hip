@@ -449,6 +449,9 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_attn_kernel(DecodeArgs a) 
 // Contract (ops/reference.py lm_sample): v = logit / T, v[eos] += eos_bias[step]; the k largest v
 // with ties broken by the LOWER id; among them the id maximising v + noise[step][id] (ties: larger
 // v, then lower id); out[step] = tok = id; pos, lens, step += 1.  One block, batch 1.
+// -0.0 and +0.0 are one value, as in the reference's stable sort (the lower id wins): value()
+// turns -0.0 into +0.0, so the radix keys, the tie cut and the Gumbel comparison see one zero
+// (fkey alone would rank -0.0 strictly below +0.0).
 constexpr int SAMPLE_THREADS = 1024;
 
 CM_DEVICE unsigned fkey(float f) {                  // order-preserving float -> uint32
@@ -475,7 +478,7 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) lm_sample_kernel(const void* _
     const float l = F32 ? reinterpret_cast<const float*>(logits)[i] : bf2f(reinterpret_cast<const uint16_t*>(logits)[i]);
     float v = l / temp;
     if (i == eos) v += eb;
-    return v;
+    return v + 0.0f;                                // -0.0 -> +0.0 (round to nearest), every other v unchanged
   };
   // ---- radix select of the k-th largest key, 8 bits per pass from the top
   unsigned prefix = 0, mask = 0, rem = (unsigned)min(k, V);

@@ -5,7 +5,8 @@
 //   micro-batch of players' guesses is one launch.
 // * pair_cosine: row-wise cosine of two embedding matrices (MiniLM scorer).
 // * cosine_gemv (K15): table . v / (|row| |v|) for most_similar, one wave per row.
-// * mean_pool_l2 (K16 tail): masked mean over tokens + L2 normalisation, one block per row.
+// * mean_pool_l2 (K16 tail): masked mean over tokens + L2 normalisation, one block per row; a row
+//   with lens == 0 is the zero vector.
 // * gaussian_blur (K17): uint8 images (the served JPEG content), radius <= 48: ONE LDS-tiled
 //   kernel per 32x32 output tile — the clamped input tile + halo is staged in LDS once, the
 //   horizontal pass writes an f32 LDS intermediate, the vertical pass reads it (no global
@@ -97,7 +98,8 @@ CM_DEVICE float f_from_orderable(uint32_t o) {
   return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
 CM_DEVICE unsigned long long tk_key(float score, int row) {
-  return ((unsigned long long)f_orderable(score) << 32) | (unsigned long long)(~(uint32_t)row);
+  // score + 0.0f: -0.0 (an underflowing negative dot) is the same score as +0.0, the lower row first
+  return ((unsigned long long)f_orderable(score + 0.0f) << 32) | (unsigned long long)(~(uint32_t)row);
 }
 
 // descending bitonic sort of TK_CHUNK keys in LDS by TK_THREADS threads (one pair each per step)
@@ -168,13 +170,16 @@ __global__ void mean_pool_l2_kernel(const uint16_t* __restrict__ h, const int* _
                                     float* __restrict__ out, int T, int D) {
   extern __shared__ float buf[];   // [D] + [64]
   const int b = blockIdx.x;
-  const int L = max(1, min(T, lens[b]));
+  // lens > T clamps to T.  An empty row (lens <= 0) reads no token: its mean is 0 and the 1e-12
+  // clamp below makes the output the zero vector, as ops/reference.py mean_pool_l2 (it used to
+  // return the normalised first token, which is padding there)
+  const int L = max(0, min(T, lens[b]));
   float* red = buf + D;
   float ss = 0.f;
   for (int d = threadIdx.x; d < D; d += blockDim.x) {
     float s = 0.f;
     for (int t = 0; t < L; ++t) s += bf2f(h[((long long)b * T + t) * D + d]);
-    s /= (float)L;
+    s /= (float)max(L, 1);
     buf[d] = s;
     ss = fmaf(s, s, ss);
   }
@@ -441,7 +446,11 @@ __global__ void silu_bf16_kernel(uint16_t* __restrict__ x, long long n8) {
   float f[8];
   unpack8(reinterpret_cast<uint4*>(x)[i], f);
 #pragma unroll
-  for (int k = 0; k < 8; ++k) f[k] = f[k] / (1.f + __expf(-f[k]));
+  for (int k = 0; k < 8; ++k) {
+    // below -80 exp(-x) leaves fp32's range (x / inf = -0.0 from -88.8 down) while x e^x is still a
+    // bf16 value down to -97: there 1 + e^x == 1 in fp32, and expf keeps the denormal e^x
+    f[k] = f[k] < -80.f ? f[k] * expf(f[k]) : f[k] / (1.f + __expf(-f[k]));
+  }
   reinterpret_cast<uint4*>(x)[i] = pack8(f);
 }
 

@@ -264,7 +264,9 @@ def silu(x):
 
 
 def mean_pool_l2(hidden, lens):
-    """Masked mean over tokens then L2-normalise: hidden [B, T, D], lens [B] -> [B, D] fp32."""
+    """Masked mean over tokens then L2-normalise: hidden [B, T, D], lens [B] -> [B, D] fp32.
+    ``lens > T`` counts T tokens; a row with ``lens == 0`` is the zero vector (no token is read),
+    here and in misc.hip's mean_pool_l2_kernel."""
     T = hidden.shape[1]
     m = (torch.arange(T, device=hidden.device)[None, :] < lens.to(hidden.device)[:, None]).float()
     s = (hidden.float() * m[..., None]).sum(1) / m.sum(1, keepdim=True).clamp_min(1.0)
@@ -275,7 +277,9 @@ def lm_sample(logits, noise, eos_bias, eos: int, temperature: float, k: int, ste
     """Decode-step sampler (the contract of lm.hip's lm_sample_kernel), graph-capturable: v =
     logits / T with the step's EOS bias added at ``eos``; the k largest v (stable: ties keep the
     LOWER id); the id maximising v + noise[step] among them (first in that order on ties); then
-    out[step] = tok = id and pos, lens, step advance by one."""
+    out[step] = tok = id and pos, lens, step advance by one.  -0.0 and +0.0 are equal in that
+    sort, so of two zeros the lower id ranks first whatever their signs; the kernel turns -0.0
+    into +0.0 before it builds its keys to rank them the same way."""
     lg = logits.float().reshape(1, -1) / temperature
     V = lg.shape[-1]
     if 0 <= eos < V:

@@ -1,5 +1,6 @@
 """Instruments for localised kernel errors, shared by test_kernel_oracle.py (CPU: the instruments
-themselves, proven on planted bugs) and test_kernel_edges_gpu.py (the HIP kernels).
+themselves, proven on planted bugs) and test_kernel_edges_gpu.py, test_kernel_edges_decode_gpu.py
+and test_kernel_edges_scorer_gpu.py (the HIP kernels).
 
 A whole-tensor ``|out - ref| / |ref|`` under 1e-2 passes a kernel that drops the bias of one row,
 leaves one padding key unmasked or normalises one row group with another's statistics.  Three
@@ -23,7 +24,7 @@ never hand a kernel a pointer whose tile-sized neighbourhood is unallocated.
 The ideal kernel (fp64 math, rounded only where the kernels' own headers say they round: the bf16
 output, the bf16 scaled Q and P of attention, the bf16 folded W*gamma of the LayerNorm fold, the
 bf16 normalised A rows of the GroupNorm fold, e4m3 Q/K/V/P of the fp8 attention) must stay under
-HALF the bound in every block of every case of :mod:`test_kernel_edges_gpu`; test_kernel_oracle.py
+HALF the bound in every block of every case of the three GPU files; test_kernel_oracle.py
 asserts that.  Its worst block, measured on the CPU over those cases (the table
 test_kernel_oracle.py::test_floor_table prints with ``-s``):
 
@@ -38,6 +39,18 @@ test_kernel_oracle.py::test_floor_table prints with ``-s``):
     layer / rms / embed   one row                    1e-2     2.25e-3
     group_norm            16 pixels x one group      1e-2     3.05e-3
     rope_kv               one token x one head       1e-2     1.91e-3
+    GEMV (lm.hip)         one row x 4 columns (2)    1e-2     3.83e-3   (2: the gated 8-row template)
+    GEMV + RMSNorm        one row x 4 columns (2)    1e-2     3.27e-3
+    GEMV, batched         one row x 4 columns        1e-2     3.81e-3
+    M = 8 | 9 linear      one row x 4 columns        1e-2     3.06e-3
+    M = 8 | 9 ln_linear   one row                    1.5e-2   2.80e-3   (4 columns: 8.1e-3 at M = 8, so the row)
+    decode, d = 128 / L > 4096   one query x d       2e-2     8.93e-3   (with a bf16 P)
+    mean_pool_l2          one row                    1e-5     1.39e-7   (the fp32 evaluation; fp32 output)
+
+The GEMV keeps the kernel's own block, one row x the columns of one thread block: the bf16 store
+alone stays under half of 1e-2 there.  The four cosine kernels are held to an absolute 1e-5
+against fp64 (COS_ATOL) for fp32 and bf16 tables alike; the same formula in fp32 is within 2.4e-7
+on every case.  The sampler, cosine_topk's order and the byte-moving glue kernels are exact.
 
 Nothing here is calibrated against what the HIP kernels return.
 
@@ -405,6 +418,13 @@ DECODE_L = (1, 127, 128, 129)
 DECODE_GROUPS = (1, 2, 4)
 
 
+def decode_key_gain(d) -> float:
+    """the dominant key is this times its query's direction: 4 at d = 64 and the same score
+    (gain * sqrt(d)) at d = 128, where a gain of 4 would put the bf16-P model of a head that does
+    not follow the direction at 1.3e-2, over half the bound (the key's norm scales its rounding)"""
+    return 4.0 * (64.0 / d) ** 0.5
+
+
 def decode_data(L, group, d=64, Hk=2):
     """q [3, H, d], caches [3, L, Hk, d], lens = [L, 1, mid]: the last valid key dominant, the
     first one past ``lens`` dominant with V = SENTINEL_V"""
@@ -415,7 +435,7 @@ def decode_data(L, group, d=64, Hk=2):
     u = rnd(B, Hk, d, seed=s + 3)
     q[:, ::2] = (u.repeat_interleave(group, 1)[:, ::2].float() + 0.25 * q[:, ::2].float()).to(BF16)
     for b, n in enumerate(lens):
-        kc[b, n - 1] = (4 * u[b].float()).to(BF16)
+        kc[b, n - 1] = (decode_key_gain(d) * u[b].float()).to(BF16)
         vc[b, n - 1] = LAST_V
         if n < L:
             kc[b, n] = kc[b, n - 1]
@@ -463,3 +483,392 @@ def rope64(qkv, pos0, H, Hk, d, theta=10000.0):
     pos = torch.tensor(pos0)[:, None] + torch.arange(T)[None, :]
     return (ref.rope(x[:, :, :H], pos, theta, dtype=F64), ref.rope(x[:, :, H:H + Hk], pos, theta, dtype=F64),
             x[:, :, H + Hk:].to(F64))
+
+
+# ------------------------------------------------------------------------------ GEMV (lm.hip)
+GEMV_STEP = 2048             # k elements one pass of the 256 lanes covers (8 each)
+GATED = ("geglu", "swiglu")
+
+
+class GemvCase(NamedTuple):
+    M: int
+    N: int            # outputs (W has 2N rows for the gated activations)
+    K: int
+    act: str
+
+    @property
+    def gated(self):
+        return self.act in GATED
+
+    @property
+    def cols(self):
+        """output columns one block of gemv_kernel owns: 4, or 2 for the gated M = 8 template"""
+        return 2 if self.gated and self.M > 4 else 4
+
+    @property
+    def block(self):
+        return (1, self.cols)
+
+    @property
+    def id(self):
+        return f"{self.M}x{self.N}x{self.K}-{self.act}"
+
+
+GEMV_N = (1, 5, 7, 70)
+GEMV_K = (8, 72, 2048, 2056, 4096, 4104, 6152)      # one lane / one pass / the two-chunk loop once, twice, +- a lane
+
+
+def gemv_cases() -> list:
+    """per (M template, gated or not): every N at K = 72 and every K at N = 7 (gated: 3), the rows
+    M of that template and its two activations taking turns.  M = 3 and 5 run the 4- and 8-row
+    templates with idle rows.  N: a block's column tail (4 wide, 2 for the gated 8-row template);
+    K: see GEMV_K."""
+    cases = []
+    for Ms in ((1,), (2,), (3, 4), (5, 8)):
+        for acts in (("none", "silu"), GATED):
+            gated = acts == GATED
+            shapes = [(N, 72) for N in GEMV_N + ((3, 9) if gated and Ms == (5, 8) else ())]
+            shapes += [(3 if gated else 7, K) for K in GEMV_K]
+            shapes = list(dict.fromkeys(shapes))
+            cases += [GemvCase(Ms[i % len(Ms)], N, K, acts[(i // len(Ms)) % 2]) for i, (N, K) in enumerate(shapes)]
+    return cases
+
+
+GEMV_CASES = gemv_cases()
+GEMV_SIMT_CASE = GemvCase(3, 7, 12, "silu")                                # K % 8 != 0: not the GEMV's
+RMS_CASES = [GemvCase(M, 7, K, act) for M in (1, 5, 8) for K in (8, 2056, 4104) for act in ("none", "swiglu")]
+RMS_ROW_SCALE = (1.0, 2.0, 0.5)      # row m of x is scaled by 3 * RMS_ROW_SCALE[m % 3]: every row its own 1/rms
+BMM_GEMV_CASES = [(3, M, 5, 72) for M in (1, 8)]                           # (batch, M, N, K)
+BMM_ALPHA = 0.37
+DISPATCH_M = (8, 9)                  # the last GEMV row count and the first MFMA one
+DISPATCH_NK = (72, 128)              # N % 8 == 0 (statistics), K = Ca + Cb of linear_cat
+
+
+def gemv_inputs(c: GemvCase):
+    """x, w, bias, residual (bf16, CPU)"""
+    Nw = 2 * c.N if c.gated else c.N
+    s = 8000 + 7 * c.M + 3 * c.N + c.K + len(c.act)
+    return (rnd(c.M, c.K, seed=s), rnd(Nw, c.K, scale=c.K ** -0.5, seed=s + 1), rnd(Nw, scale=0.1, seed=s + 2),
+            rnd(c.M, c.N, seed=s + 3))
+
+
+def rms_inputs(c: GemvCase):
+    """x (rows scaled by 3 * RMS_ROW_SCALE), gamma, w, bias, residual"""
+    x, w, b, r = gemv_inputs(c)
+    sc = torch.tensor([3 * RMS_ROW_SCALE[m % 3] for m in range(c.M)])
+    x = (x.float() * sc[:, None]).to(BF16)
+    return x, rnd(c.K, scale=0.3, shift=1.0, seed=c.K + c.M), w, b, r
+
+
+def rms_linear64(x, g, w, b, r, act, eps=1e-5):
+    return ref.linear(ref.rms_norm(x, g, eps, dtype=F64), w, b, residual=r, act=act, dtype=F64)
+
+
+def gemv_model(c: GemvCase, x, w, b, r, gamma=None, eps=1e-5, skip_tail_column=False, drop_last_chunk=False,
+               rms_of_row0=False) -> Guarded:
+    """gemv_kernel in fp64 with its one rounding (the bf16 store), written into a guarded output
+    as the kernel writes it.  The planted bugs: ``skip_tail_column`` never stores the last column
+    of a partial block, ``drop_last_chunk`` leaves the 8 k-elements at K - 8 out of every dot
+    product, ``rms_of_row0`` scales every row by row 0's 1/rms."""
+    xd, wd = x.to(F64), w.to(F64)
+    scale = torch.ones(c.M, 1, dtype=F64)
+    if gamma is not None:
+        ss = (xd * xd).mean(-1, keepdim=True)
+        scale = (ss[:1].expand_as(ss) if rms_of_row0 else ss).add(eps).rsqrt()
+        xd = xd * gamma.to(F64)
+    if drop_last_chunk:
+        xd = xd.clone()
+        xd[:, c.K - 8:] = 0
+    y = (xd @ wd.t()) * scale + b.to(F64)
+    if c.gated:
+        h, g = y.chunk(2, dim=-1)
+        y = h * (torch.nn.functional.gelu(g) if c.act == "geglu" else torch.nn.functional.silu(g))
+    elif c.act == "silu":
+        y = torch.nn.functional.silu(y)
+    y = y + r.to(F64)
+    out = guarded((c.M, c.N))
+    n = c.N - 1 if skip_tail_column and c.N % c.cols else c.N
+    out.view[:, :n] = y[:, :n].to(BF16)
+    return out
+
+
+# ------------------------------------------------------------------------------ decode attention, the edges
+# (L, group, d, lens or None): every head dim and the odd / largest group at a span's edge; above
+# L = 4096 decode_splits stays at 32 splits and a split's span grows to 256 keys
+DECODE_EDGE_CASES = ([(L, g, 128, None) for L in (127, 129) for g in (3, 8)] +
+                     [(L, 2, 64, (L, 1, 257)) for L in (4097, 4224)])
+
+
+def decode_edge_data(L, group, d, lens):
+    """decode_data with the dominant last key / sentinel V construction at ``lens``"""
+    q, kc, vc, ln = decode_data(L, group, d)
+    if lens is None:
+        return q, kc, vc, ln
+    s = 4500 + 3 * L + group
+    kc, vc = rnd(3, L, 2, d, seed=s + 1), rnd(3, L, 2, d, seed=s + 2)
+    u = rnd(3, 2, d, seed=4000 + 3 * L + group + 3)           # decode_data's directions (its q follows them)
+    for b, n in enumerate(lens):
+        kc[b, n - 1] = (decode_key_gain(d) * u[b].float()).to(BF16)
+        vc[b, n - 1] = LAST_V
+        if n < L:
+            kc[b, n] = kc[b, n - 1]
+            vc[b, n:] = SENTINEL_V
+    return q, kc, vc, list(lens)
+
+
+# ------------------------------------------------------------------------------ sampler (lm_sample_kernel)
+SAMPLE_CHUNK = 1024          # ids one pass of the tie cut covers
+PROBE_NOISE = 1e4
+NEG_INF = -math.inf
+
+
+class SampleCase(NamedTuple):
+    name: str
+    logits: torch.Tensor      # fp32 [V]
+    k: int
+    eos: int
+    eos_bias: float
+    signed_zero: bool = False
+
+
+def _neg(V, seed):
+    """distinct negative logits, none of them a zero"""
+    return -(0.5 + torch.rand(V, generator=torch.Generator().manual_seed(seed)) * 6)
+
+
+def sampler_cases() -> list:
+    cs = []
+    for V in (1, 255, 1024, 1025, 2049):
+        for k in dict.fromkeys((1, 40, V, V + 5)):
+            cs.append(SampleCase(f"rand-V{V}-k{k}", rnd(V, scale=3.0, seed=V + k, dtype=torch.float32), k, 7 % V, 0.0))
+    for k in (40, 1500):                                     # all equal: the cut keeps ids 0 .. k - 1
+        cs.append(SampleCase(f"equal-k{k}", torch.full((2049,), 1.5), k, 7, 0.0))
+    lg = _neg(2049, 1)                                       # 20 above, 1500 tied at the k-th place: `need` = 1200
+    lg[100:1600] = 1.0                                       # crosses the chunk of ids < 1024 (924 tied there)
+    lg[2000:2020] = 5.0 + torch.arange(20) / 8
+    cs.append(SampleCase("tie-across-chunks", lg, 1220, 7, 0.0))
+    # -0.0 and +0.0 at the k-th place (k = 3: the contract keeps {2, 5, 9}, a key order that puts
+    # -0.0 below +0.0 keeps {2, 9, 11} / {2, 5, 11})
+    for name, z in (("minus-zero-at-lower-id", (-0.0, 0.0, 0.0)), ("minus-zero-at-higher-id", (0.0, -0.0, 0.0))):
+        lg = _neg(300, 2)
+        lg[2] = 4.0
+        lg[5], lg[9], lg[11] = z
+        cs.append(SampleCase(name, lg, 3, 7, 0.0, signed_zero=True))
+    lg = rnd(255, scale=3.0, seed=3, dtype=torch.float32)    # members that never win
+    lg[3] = lg[200] = NEG_INF
+    cs.append(SampleCase("neg-inf-members", lg, 255, 7, NEG_INF))
+    for eos in (0, 1024):
+        cs.append(SampleCase(f"eos-at-{eos}", rnd(1025, scale=3.0, seed=4, dtype=torch.float32), 40, eos, 5.0))
+    return cs
+
+
+SAMPLER_CASES = sampler_cases()
+
+
+def sample_values(logits, T, eos, eos_bias) -> torch.Tensor:
+    """v of the contract: logits.float() / T with the EOS bias (fp32, as ops.reference.lm_sample)"""
+    v = logits.float().reshape(-1) / T
+    if 0 <= eos < v.numel():
+        v[eos] += eos_bias
+    return v
+
+
+def rank_probes(logits, T, k, eos, eos_bias):
+    """noise rows [n, 1, V] that put PROBE_NOISE on the id ranked k - 1, k and k + 1 (1-based, in
+    the reference's stable descending order) and 0 elsewhere, then one row of Gumbel noise; with
+    them the probed ids and whether each is inside the top-k set"""
+    v = sample_values(logits, T, eos, eos_bias)
+    V = v.numel()
+    order = torch.sort(v, descending=True, stable=True).indices
+    kk = min(k, V)
+    ranks = [r for r in (kk - 1, kk, kk + 1) if 1 <= r <= V]
+    noise = torch.zeros(len(ranks) + 1, 1, V)
+    ids = [int(order[r - 1]) for r in ranks]
+    for i, t in enumerate(ids):
+        noise[i, 0, t] = PROBE_NOISE
+    u = torch.rand(V, generator=torch.Generator().manual_seed(V + k)).clamp_(1e-10, 1 - 1e-7)
+    noise[-1, 0] = -torch.log(-torch.log(u))
+    return noise, ids, [r <= kk for r in ranks]
+
+
+def fkey(v: torch.Tensor) -> torch.Tensor:
+    """lm.hip's order-preserving float -> uint32 key (as int64)"""
+    u = v.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    return torch.where(u >= 0x80000000, ~u & 0xFFFFFFFF, u | 0x80000000)
+
+
+def sampler_model(logits, noise_row, T, k, eos, eos_bias, canonical_zero=True, admit=0) -> int:
+    """lm_sample_kernel's selection on the CPU: top-k by (key descending, id ascending), then the
+    id maximising v + noise (ties: larger v, then lower id).  The planted bugs: ``admit`` lets
+    that many more ranks into the set, ``canonical_zero=False`` keys -0.0 below +0.0."""
+    v = sample_values(logits, T, eos, eos_bias)
+    if canonical_zero:
+        v = v + 0.0
+    V = v.numel()
+    key = fkey(v)
+    order = sorted(range(V), key=lambda i: (-int(key[i]), i))[:min(k + admit, V)]
+    sc = v + noise_row.reshape(-1)
+    return min(order, key=lambda i: (-float(sc[i]), -float(v[i]), i) if not math.isnan(float(sc[i])) else (math.inf, 0, i))
+
+
+def run_sampler(fn, logits, noise, T, k, eos, eos_bias, device="cpu"):
+    """``fn`` (ops.lm_sample's signature) over every noise row, chained on the device counters:
+    (out, tok, pos, lens, step)"""
+    n = noise.shape[0]
+    step = torch.zeros(1, device=device, dtype=torch.long)
+    out = torch.full((n, 1), -1, device=device, dtype=torch.long)
+    tok = torch.zeros(1, device=device, dtype=torch.long)
+    pos = torch.zeros(1, device=device, dtype=torch.int32)
+    lens = torch.ones(1, device=device, dtype=torch.int32)
+    eb = torch.full((n,), eos_bias, device=device)
+    lg, nz = logits.to(device).reshape(1, -1), noise.to(device)
+    for _ in range(n):
+        fn(lg, nz, eb, eos, T, k, step, out, tok, pos, lens)
+    return out.flatten().tolist(), int(tok), int(pos), int(lens), int(step)
+
+
+# ------------------------------------------------------------------------------ scorer (misc.hip)
+COS_ATOL = 1e-5              # the fp32 test's absolute tolerance, for bf16 tables too: both sides share the inputs
+COS_FLOOR = 5e-6             # the same formula in fp32 stays under this (test_kernel_oracle.py)
+COS_D = (1, 8, 63, 64, 65, 300)
+COS_N = (1, 4, 5)
+COS_ROWS = 8                 # table rows; row COS_ZERO_ROW is all zero, the last one is used as an index
+COS_ZERO_ROW = 3
+COS_PAIRS = ((COS_ROWS - 1, 0), (2, 2), (COS_ZERO_ROW, 1), (0, 1), (4, 5))
+
+
+def cos_table(D, dtype, rows=COS_ROWS, seed=0):
+    t = rnd(rows, D, seed=9000 + D + seed, dtype=torch.float32)
+    if rows > COS_ZERO_ROW:
+        t[COS_ZERO_ROW] = 0
+    return t.to(dtype)
+
+
+def cosine64(a, b):
+    """fp64 cosine of rows, 0 where a norm is 0 (the kernels' clamp)"""
+    a, b = a.to(F64), b.to(F64)
+    return (a * b).sum(-1) / (a.norm(dim=-1) * b.norm(dim=-1)).clamp_min(1e-12)
+
+
+def cosine32(a, b):
+    """the kernels' formula in fp32: fp32 products and sums, sqrt(na) * sqrt(nb), clamp 1e-12"""
+    a, b = a.float(), b.float()
+    return (a * b).sum(-1) / ((a * a).sum(-1).sqrt() * (b * b).sum(-1).sqrt()).clamp_min(1e-12)
+
+
+POOL_D = (8, 384, 1000)
+POOL_LENS = (9, 1, 4, 0, 12)
+POOL_T = 9
+BOUND["pool"] = 1e-5         # per row, fp32 out: 9 + ~12 fp32 roundings per element (test_kernel_oracle.py measures the floor)
+
+
+def pool_inputs(D):
+    """hidden [5, 9, D] bf16 with NaN in every token at or past lens[b] (the empty row keeps token
+    0 finite: the kernel may not use it either), and the lengths"""
+    h = rnd(len(POOL_LENS), POOL_T, D, seed=9500 + D)
+    for b, n in enumerate(POOL_LENS):
+        h[b, max(n, 1):] = math.nan
+    return h, torch.tensor(POOL_LENS, dtype=torch.int32)
+
+
+def mean_pool64(h, lens, min_len=0):
+    """fp64 masked mean and normalisation; an empty row is the zero vector.  ``min_len=1``: the
+    planted L = max(1, .) rule"""
+    out = torch.zeros(h.shape[0], h.shape[2], dtype=F64)
+    for b, n in enumerate(lens.tolist()):
+        n = max(min_len, min(n, h.shape[1]))
+        if n > 0:
+            s = h[b, :n].to(F64).mean(0)
+            out[b] = s / s.norm().clamp_min(1e-12)
+    return out
+
+
+def mean_pool32(h, lens):
+    out = torch.zeros(h.shape[0], h.shape[2])
+    for b, n in enumerate(lens.tolist()):
+        n = min(n, h.shape[1])
+        if n > 0:
+            s = torch.zeros(h.shape[2])
+            for t in range(n):
+                s = s + h[b, t].float()
+            s = s / float(n)
+            out[b] = s * (1.0 / (s * s).sum().sqrt().clamp_min(1e-12))
+    return out
+
+
+TOPK_CHUNK = 2048
+TOPK_D = 8
+TOPK_CASES = ((1, 1), (2047, 5), (2048, 5), (2049, 1024), (2049, 5), (1024, 1024), (6145, 1024), (6145, 51))   # (V, k)
+TOPK_TOL = 2e-5              # two scores COS_ATOL from their fp64 values may swap
+
+
+def topk_inputs(V, dtype):
+    """table [V, 8], query, the rows that are bit-identical copies of the query (ascending)"""
+    t = rnd(V, TOPK_D, seed=9700 + V, dtype=torch.float32).to(dtype)
+    vec = rnd(TOPK_D, seed=9701, dtype=torch.float32).to(dtype)
+    if V > COS_ZERO_ROW:
+        t[COS_ZERO_ROW] = 0
+    planted = sorted({r for r in (2047, 2048, 4096, V - 1) if 0 <= r < V and r != COS_ZERO_ROW})
+    for r in planted:
+        t[r] = vec
+    return t, vec, planted
+
+
+def topk_model(s: torch.Tensor, k: int, padding_surfaces=False):
+    """topk_partial_kernel / topk_merge_kernel on scores ``s``: 2048-row chunks padded with the
+    key 0, each sorted and cut to k, merged until one is left.  A key is (orderable score, ~row);
+    the planted bug gives padding the key of a score of +0.0 at row 0xffffffff - slot instead"""
+    V = s.numel()
+    keys = [(int(fkey(s[i:i + 1] + 0.0)), 0xFFFFFFFF - i) for i in range(V)]
+    chunks = []
+    for c0 in range(0, V, TOPK_CHUNK):
+        ch = keys[c0:c0 + TOPK_CHUNK]
+        pad = TOPK_CHUNK - len(ch)
+        ch = ch + [((0x80000000, j) if padding_surfaces else (0, 0)) for j in range(pad)]
+        chunks.append(sorted(ch, reverse=True)[:k])
+    flat = [x for ch in chunks for x in ch]
+    best = sorted(flat, reverse=True)[:k]
+    return [0xFFFFFFFF - r for _, r in best]
+
+
+def check_topk(vals, idx, s64, k, planted):
+    """the assertions of a cosine_topk result against the fp64 scores"""
+    V = s64.numel()
+    vals, idx = vals.to("cpu", F64), idx.cpu().long()
+    assert idx.numel() == k and len(set(idx.tolist())) == k, "rows repeat"
+    assert int(idx.min()) >= 0 and int(idx.max()) < V, "a row outside the table (a padding key surfaced)"
+    assert bool((vals[1:] <= vals[:-1]).all()), "vals must be non-increasing"
+    top = torch.sort(s64, descending=True).values
+    assert float((vals - s64[idx]).abs().max()) <= COS_ATOL
+    assert float((s64[idx] - top[:k]).abs().max()) <= TOPK_TOL
+    must = (s64 > top[k - 1] + TOPK_TOL).nonzero().flatten().tolist()
+    assert set(must) <= set(idx.tolist()), "a row clearly inside the top k is missing"
+    n = min(len(planted), k)
+    assert idx[:n].tolist() == planted[:n], "copies of the query come first, the lower row first"
+    assert n == 0 or bool((vals[:n] == vals[0]).all())
+
+
+# ------------------------------------------------------------------------------ glue (misc.hip)
+def all_bf16(with_inf=True) -> torch.Tensor:
+    """every finite bf16 bit pattern (65280 of them, a multiple of 8), then -inf and +inf"""
+    x = torch.arange(-32768, 32768, dtype=torch.int32).to(torch.int16).view(BF16)
+    fin = x[torch.isfinite(x.float())]
+    assert fin.numel() == 65280
+    return torch.cat([fin, torch.tensor([-math.inf, math.inf], dtype=BF16)]) if with_inf else fin
+
+
+def bf16_ordinal(t: torch.Tensor) -> torch.Tensor:
+    """bf16 -> integers in which neighbouring values differ by one (both zeros are 0)"""
+    i = t.contiguous().view(torch.int16).to(torch.int64)
+    return torch.where(i < 0, -(i & 0x7FFF), i)
+
+
+def silu64(x):
+    xd = x.to(F64)
+    return xd / (1 + torch.exp(-xd))
+
+
+GLUE_ROWS = (1, 3)
+GLUE_D = (8, 24)
+COPY_BYTES = (1, 15, 16, 17, 4096 + 7)
+FINALIZE_N = (1, 3, 4, 5, 4099)

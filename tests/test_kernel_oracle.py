@@ -1,7 +1,11 @@
 """The instruments of kernel_oracle.py, proven on the CPU with ``ops.reference`` as the kernel:
 the ideal kernel (fp64 math, one rounding where the HIP kernels round) stays under half the bound
-in every block of every case test_kernel_edges_gpu.py runs, and each planted bug -- all of which
-the whole-tensor error of tests/test_kernels_gpu.py lets through -- fails its check."""
+in every block of every case test_kernel_edges_gpu.py, test_kernel_edges_decode_gpu.py and
+test_kernel_edges_scorer_gpu.py run, and each planted bug -- those of the first file all get past
+the whole-tensor error of tests/test_kernels_gpu.py -- fails its check.  The sampler, the top-k
+and mean_pool_l2 have models of the kernels' own selection rules here; their planted bugs are the
+ones those kernels had or could have (a tie cut one rank too wide, -0.0 keyed below +0.0, a
+padding key that surfaces, the first token of an empty row)."""
 import math
 
 import pytest
@@ -13,11 +17,12 @@ from cassmantle_amd.ops import reference as ref
 from kernel_oracle import BF16, BOUND, F64, bf16_round, block_rel_err
 from test_gemm_menu import header_rows
 
-FLOOR = {}      # family -> the ideal kernel's worst block over the cases run so far
+FLOOR = {}      # table row -> (family, the ideal kernel's worst block over the cases run so far)
 
 
-def floor(family, err, what):
-    FLOOR[family] = max(FLOOR.get(family, 0.0), err)
+def floor(family, err, what, row=None):
+    """``row``: a line of its own in the table for cases that share a family's bound"""
+    FLOOR[row or family] = (family, max(FLOOR.get(row or family, (family, 0.0))[1], err))
     assert err < 0.5 * BOUND[family], (family, what, err)
 
 
@@ -103,15 +108,6 @@ def test_ideal_norms_and_rope():
         qkv = ko.rnd(B, T, (H + 2 * Hk) * d, seed=T + d)
         for y64 in ko.rope64(qkv, pos0, H, Hk, d):
             floor("rope", block_rel_err(bf16_round(y64), y64, (1, 1, 1, None)), (B, T, H, Hk, d))
-
-
-def test_floor_table():
-    """prints the table of kernel_oracle.py's docstring (run the whole file with -s)"""
-    if not FLOOR:
-        pytest.skip("run together with the ideal-kernel tests")
-    for fam in sorted(FLOOR):
-        print(f"{fam:12s} bound {BOUND[fam]:.3g}  ideal kernel's worst block {FLOOR[fam]:.2e}")
-        assert FLOOR[fam] < 0.5 * BOUND[fam]
 
 
 # ------------------------------------------------------------------------------ planted bugs
@@ -258,3 +254,213 @@ def test_attention_without_a_valid_key_is_zero():
     od = ref.decode_attention(qd, kc, vc, torch.tensor([9, 0, 4]), 0.25)
     assert torch.isfinite(od.float()).all() and not od[1].any() and od[0].any() and od[2].any()
     assert torch.equal(ops.decode_attention(qd, kc, vc, torch.tensor([9, 0, 4]), 0.25), od)
+
+
+# ------------------------------------------------------------------------------ decode, sampler, scorer: the ideal kernel passes
+def test_ideal_gemv():
+    """gemv_kernel's blocks are one row x 4 columns (2 for the gated 8-row template); the bf16 store
+    alone stays under half the bound there, so the family keeps its narrow block"""
+    assert 80 <= len(ko.GEMV_CASES) <= 100 and len({c.id for c in ko.GEMV_CASES}) == len(ko.GEMV_CASES)
+    for c in ko.GEMV_CASES:
+        x, w, b, r = ko.gemv_inputs(c)
+        g = ko.gemv_model(c, x, w, b, r)
+        ko.check_guards(g)
+        floor("gemm", block_rel_err(g.view, ko.linear64(x, w, b, r, c.act), c.block), c.id, "gemv")
+    for c in ko.RMS_CASES:
+        x, gam, w, b, r = ko.rms_inputs(c)
+        g = ko.gemv_model(c, x, w, b, r, gamma=gam)
+        floor("gemm", block_rel_err(g.view, ko.rms_linear64(x, gam, w, b, r, c.act), c.block), c.id, "gemv + rms")
+    for Bt, M, N, K in ko.BMM_GEMV_CASES:
+        a, b = ko.rnd(Bt, M, K, seed=M), ko.rnd(Bt, N, K, seed=M + 1)
+        y64 = ko.BMM_ALPHA * a.to(F64) @ b.to(F64).transpose(1, 2)
+        floor("gemm", block_rel_err(bf16_round(y64), y64, (1, 1, 4)), ("bmm", M), "gemv bmm_nt")
+    N, K = ko.DISPATCH_NK
+    for M in ko.DISPATCH_M + (9,):                             # (9: the row_stats producer's inputs)
+        x, w, b, r = ko.gemv_inputs(ko.GemvCase(M, N, K, "none"))
+        y64 = ko.linear64(x, w, b, r)
+        floor("gemm", block_rel_err(bf16_round(y64), y64, (1, 4)), ("dispatch", M), "gemv | mfma")
+        x, g, be, w, b = ko.ln_fold_inputs(M, N, K, seed=M)
+        y64 = ko.ln_linear64(x, g, be, w, b)
+        floor("ln_fold", block_rel_err(ko.ideal_ln_fold(x, g, be, w, b), y64, (1, None)), ("dispatch ln", M), "gemv | mfma ln")
+        xn = ref.layer_norm(x, g, be, 1e-5, dtype=F64).to(BF16)                  # <= 8 rows: LayerNorm kernel, then the GEMV
+        floor("ln_fold", block_rel_err(bf16_round(ko.linear64(xn, w, b)), y64, (1, None)), ("dispatch ln", M), "gemv | mfma ln")
+
+
+def test_ideal_decode_attention_edges():
+    for L, g, d, lens in ko.DECODE_EDGE_CASES:
+        q, kc, vc, ln = ko.decode_edge_data(L, g, d, lens)
+        assert kc.numel() <= 3 * 4224 * 2 * 64 and (lens is None or ln == list(lens))
+        o64 = ko.decode64(q, kc, vc, ln)
+        floor("decode", block_rel_err(ko.ideal_attention(q[:, None], kc, vc, ln)[:, 0], o64, (1, 1, None)), (L, g, d), "decode edges")
+        for bug in ({"extra_key": True}, {"drop_last": True}):
+            assert block_rel_err(ko.ideal_attention(q[:, None], kc, vc, ln, **bug)[:, 0], o64, (1, 1, None)) > BOUND["decode"]
+
+
+SAMPLER_VARIANTS = [(dt, T) for dt in (BF16, torch.float32) for T in (1.0, 0.8)]
+
+
+def test_rank_probes_hold_for_the_reference_and_the_ideal_sampler():
+    """ops.reference.lm_sample under the probes: the ids ranked k - 1 and k win, the one ranked
+    k + 1 does not (where their values are finite), and the model of the kernel agrees with it"""
+    for c in ko.SAMPLER_CASES:
+        for dt, T in SAMPLER_VARIANTS:
+            lg = c.logits.to(dt)
+            noise, ids, inside = ko.rank_probes(lg, T, c.k, c.eos, c.eos_bias)
+            out = ko.run_sampler(ref.lm_sample, lg, noise, T, c.k, c.eos, c.eos_bias)
+            assert out[1:] == (out[0][-1], len(out[0]), 1 + len(out[0]), len(out[0]))
+            v = ko.sample_values(lg, T, c.eos, c.eos_bias)
+            for got, t, ins in zip(out[0], ids, inside):
+                if math.isfinite(float(v[t])):
+                    assert (got == t) == ins, (c.name, dt, T, got, t, ins)
+            model = [ko.sampler_model(lg, noise[i], T, c.k, c.eos, c.eos_bias) for i in range(noise.shape[0])]
+            assert model == out[0], (c.name, dt, T)
+
+
+def test_sampler_cases_reach_the_paths_they_are_for():
+    by = {c.name: c for c in ko.SAMPLER_CASES}
+    assert {c.logits.numel() for c in ko.SAMPLER_CASES} >= {1, 255, 1024, 1025, 2049}
+    c = by["tie-across-chunks"]
+    v = ko.sample_values(c.logits, 1.0, c.eos, c.eos_bias)
+    order = torch.sort(v, descending=True, stable=True).indices
+    kth = float(v[order[c.k - 1]])
+    tied = (v == kth).nonzero().flatten()
+    need = c.k - int((v > kth).sum())
+    assert tied.numel() == 1500 and need > int((tied < ko.SAMPLE_CHUNK).sum()) and int(order[c.k - 1]) >= ko.SAMPLE_CHUNK
+    c = by["equal-k1500"]
+    assert int(torch.sort(c.logits, descending=True, stable=True).indices[c.k - 1]) == c.k - 1 >= ko.SAMPLE_CHUNK
+    for name, keep in (("minus-zero-at-lower-id", [2, 5, 9]), ("minus-zero-at-higher-id", [2, 5, 9])):
+        c = by[name]
+        for dt in (BF16, torch.float32):
+            order = torch.sort(ko.sample_values(c.logits.to(dt), 0.8, c.eos, 0.0), descending=True, stable=True).indices
+            assert sorted(order[:3].tolist()) == keep and bool((c.logits[[5, 9, 11]] == 0).all())
+    assert math.copysign(1, float(by["minus-zero-at-lower-id"].logits[5])) == -1
+    assert math.copysign(1, float(by["minus-zero-at-higher-id"].logits[9])) == -1
+
+
+def test_cosine_fp32_floor():
+    """the kernels' formula in fp32 against fp64 on every scorer case: under COS_FLOOR, half the tolerance"""
+    worst = 0.0
+    for dt in (torch.float32, BF16):
+        for D in ko.COS_D:
+            t = ko.cos_table(D, dt)
+            ia, ib = (torch.tensor(p) for p in zip(*ko.COS_PAIRS))
+            worst = max(worst, float((ko.cosine32(t[ia], t[ib]) - ko.cosine64(t[ia], t[ib])).abs().max()))
+            assert float(ko.cosine64(t[2], t[2])) == pytest.approx(1.0, abs=1e-12)
+            assert float(ko.cosine64(t[ko.COS_ZERO_ROW], t[1])) == 0.0 == float(ko.cosine32(t[ko.COS_ZERO_ROW], t[1]))
+            vec = ko.cos_table(D, dt, rows=1, seed=1)[0]
+            worst = max(worst, float((ko.cosine32(t, vec[None]) - ko.cosine64(t, vec[None])).abs().max()))
+        for V, _k in ko.TOPK_CASES:
+            t, vec, _ = ko.topk_inputs(V, dt)
+            worst = max(worst, float((ko.cosine32(t, vec[None]) - ko.cosine64(t, vec[None])).abs().max()))
+    print(f"cosine: fp32 formula's worst error {worst:.2e} (floor {ko.COS_FLOOR:g}, tolerance {ko.COS_ATOL:g})")
+    assert worst < ko.COS_FLOOR
+
+
+def test_ideal_mean_pool_and_topk():
+    for D in ko.POOL_D:
+        h, lens = ko.pool_inputs(D)
+        y64 = ko.mean_pool64(h, lens)
+        assert torch.isfinite(y64).all() and not y64[3].any()
+        floor("pool", block_rel_err(ko.mean_pool32(h, lens), y64, (1, None)), D)
+        assert torch.allclose(ref.mean_pool_l2(torch.nan_to_num(h.float()), lens).to(F64), y64, atol=1e-6)   # the contract, zero row included
+    for dt in (torch.float32, BF16):
+        for V, k in ko.TOPK_CASES:
+            t, vec, planted = ko.topk_inputs(V, dt)
+            s64 = ko.cosine64(t, vec[None])
+            s32 = ko.cosine32(t, vec[None])
+            idx = torch.tensor(ko.topk_model(s32, k))
+            ko.check_topk(s32[idx], idx, s64, k, planted)
+            assert torch.equal(idx, ref.cosine_topk(t, vec, k).indices)
+
+
+# ------------------------------------------------------------------------------ decode, sampler, scorer: planted bugs
+def test_gemv_tail_column_skipped_fails():
+    hit = 0
+    for c in ko.GEMV_CASES:
+        if c.K != 72:
+            continue
+        x, w, b, r = ko.gemv_inputs(c)
+        e = block_rel_err(ko.gemv_model(c, x, w, b, r, skip_tail_column=True).view, ko.linear64(x, w, b, r, c.act), c.block)
+        assert (e == math.inf) == (c.N % c.cols != 0), c.id
+        hit += e == math.inf
+    assert hit >= 20
+
+
+def test_gemv_last_k_chunk_dropped_fails():
+    for c in ko.GEMV_CASES:
+        if c.N not in (3, 7) or c.K == 72:
+            continue
+        x, w, b, r = ko.gemv_inputs(c)
+        e = block_rel_err(ko.gemv_model(c, x, w, b, r, drop_last_chunk=True).view, ko.linear64(x, w, b, r, c.act), c.block)
+        assert e > BOUND["gemm"], (c.id, e)
+
+
+def test_gemv_rms_of_row_0_for_every_row_fails():
+    for c in ko.RMS_CASES:
+        x, gam, w, b, r = ko.rms_inputs(c)
+        e = block_rel_err(ko.gemv_model(c, x, w, b, r, gamma=gam, rms_of_row0=True).view,
+                          ko.rms_linear64(x, gam, w, b, r, c.act), c.block)
+        assert (e > BOUND["gemm"]) == (c.M > 1), (c.id, e)
+
+
+def test_sampler_that_admits_rank_k_plus_1_fails():
+    caught = 0
+    for c in ko.SAMPLER_CASES:
+        lg = c.logits.to(BF16)
+        noise, ids, inside = ko.rank_probes(lg, 0.8, c.k, c.eos, c.eos_bias)
+        want = ko.run_sampler(ref.lm_sample, lg, noise, 0.8, c.k, c.eos, c.eos_bias)[0]
+        bad = [ko.sampler_model(lg, noise[i], 0.8, c.k, c.eos, c.eos_bias, admit=1) for i in range(noise.shape[0])]
+        if not all(inside):                                   # a rank k + 1 exists
+            assert bad != want, c.name
+            caught += 1
+    assert caught >= 15
+
+
+def test_sampler_that_ranks_minus_zero_below_zero_fails():
+    for c in ko.SAMPLER_CASES:
+        for dt, T in SAMPLER_VARIANTS:
+            lg = c.logits.to(dt)
+            noise, _, _ = ko.rank_probes(lg, T, c.k, c.eos, c.eos_bias)
+            want = ko.run_sampler(ref.lm_sample, lg, noise, T, c.k, c.eos, c.eos_bias)[0]
+            bad = [ko.sampler_model(lg, noise[i], T, c.k, c.eos, c.eos_bias, canonical_zero=False) for i in range(noise.shape[0])]
+            assert (bad != want) == c.signed_zero, (c.name, dt, T)
+
+
+def test_topk_padding_key_that_surfaces_fails():
+    t, vec, planted = ko.topk_inputs(1024, torch.float32)
+    s64, s32 = ko.cosine64(t, vec[None]), ko.cosine32(t, vec[None])
+    idx = torch.tensor(ko.topk_model(s32, 1024, padding_surfaces=True))
+    assert int(idx.max()) >= 1024
+    with pytest.raises(AssertionError):
+        ko.check_topk(s32[idx.clamp(max=1023)], idx, s64, 1024, planted)
+    t, vec, planted = ko.topk_inputs(2049, torch.float32)            # the last chunk holds one real row
+    s64, s32 = ko.cosine64(t, vec[None]), ko.cosine32(t, vec[None])
+    idx = torch.tensor(ko.topk_model(s32, 1024, padding_surfaces=True))
+    with pytest.raises(AssertionError):
+        ko.check_topk(s32[idx.clamp(max=2048)], idx, s64, 1024, planted)
+
+
+def test_mean_pool_that_reads_one_token_of_an_empty_row_fails():
+    for D in ko.POOL_D:
+        h, lens = ko.pool_inputs(D)
+        y64 = ko.mean_pool64(h, lens)
+        assert block_rel_err(ko.mean_pool64(h, lens, min_len=1), y64, (1, None)) == math.inf
+        assert block_rel_err(ko.mean_pool64(h, lens), y64, (1, None)) == 0.0
+
+
+def test_glue_instruments():
+    x = ko.all_bf16()
+    assert x.numel() == 65282 and torch.isinf(x[-2:].float()).all() and x[:-2].unique().numel() == 65279   # (-0.0 == 0.0)
+    o = ko.bf16_ordinal(torch.tensor([-0.0, 0.0, 1.0, 1.0078125, -1.0, -1.0078125], dtype=BF16))
+    assert o.tolist()[:2] == [0, 0] and o[3] - o[2] == 1 and o[5] - o[4] == -1
+    assert float(ko.silu64(torch.tensor([-0.0], dtype=BF16))[0]) == 0.0
+
+
+def test_floor_table():
+    """prints the table of kernel_oracle.py's docstring (run the whole file with -s)"""
+    if not FLOOR:
+        pytest.skip("run together with the ideal-kernel tests")
+    for row in sorted(FLOOR):
+        fam, worst = FLOOR[row]
+        print(f"{row:16s} bound {BOUND[fam]:.3g}  ideal kernel's worst block {worst:.2e}")
+        assert worst < 0.5 * BOUND[fam]
