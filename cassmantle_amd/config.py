@@ -196,6 +196,11 @@ class ModelConfig:
     lm_model: str = "tiny-lm"             # tiny-lm | mistral-7b (models/lm.py)
     lm_weights: Optional[str] = None      # HF-layout safetensors dir/file for the LM
     lm_tokenizer: Optional[str] = None    # sentencepiece model (else byte-level tokenizer)
+    # sampling noise of the LM: table (drawn on the host, one upload per prompt, batch 1) | philox
+    # (drawn in the sampler kernel from a per-sequence seed: batchable, models/lm.py)
+    lm_noise: str = "table"
+    lm_batch_max: int = 1                 # rooms' prompts decoded as one LM batch (1..8; > 1 needs lm_noise=philox)
+    lm_batch_window_ms: float = 50.0      # how long the batch leader waits for the other rooms' requests
     # --- remote generation (reference parity: HF inference endpoints, src/backend.py:24-25) ---
     remote_prompt_url: Optional[str] = None
     remote_image_url: Optional[str] = None

@@ -18,6 +18,8 @@ import hashlib
 import os
 import random
 import re
+import threading
+import time
 from typing import List, Optional, Sequence
 
 _DATA = os.path.join(os.path.dirname(os.path.dirname(__file__)), "data")
@@ -128,13 +130,87 @@ class LMPromptGenerator(PromptGenerator):
         self.max_new_tokens = max_new_tokens
         self.fallback = fallback or SyntheticPromptGenerator()
 
-    def generate(self, seed: str, is_seed: bool) -> Optional[str]:
-        text = self.lm.generate_text(seed, self.min_new_tokens, self.max_new_tokens)
+    def _finish(self, text: str, seed: str, is_seed: bool) -> Optional[str]:
         out = postprocess_generation(text, seed, echoed=False).strip()
         # a random-init LM emits no usable words; keep the 2-sentence contract
         if sum(ch.isalpha() for ch in out) < 16:
             return self.fallback.generate(seed, is_seed)
         return out
+
+    def generate(self, seed: str, is_seed: bool) -> Optional[str]:
+        return self._finish(self.lm.generate_text(seed, self.min_new_tokens, self.max_new_tokens), seed, is_seed)
+
+    def generate_many(self, seeds: Sequence[str], is_seed: Sequence[bool]) -> List[Optional[str]]:
+        """Several rooms' prompts as ONE LM batch (``lm.generate_texts``, which needs the LM's
+        ``noise="philox"``); post-processing and fallback per row."""
+        texts = self.lm.generate_texts(list(seeds), self.min_new_tokens, self.max_new_tokens)
+        return [self._finish(t, s, f) for t, s, f in zip(texts, seeds, is_seed)]
+
+
+class _PromptRequest:
+    __slots__ = ("seed", "is_seed", "done", "result", "error")
+
+    def __init__(self, seed: str, is_seed: bool) -> None:
+        self.seed, self.is_seed = seed, is_seed
+        self.done = threading.Event()
+        self.result: Optional[str] = None
+        self.error: Optional[BaseException] = None
+
+
+class BatchingPromptGenerator(PromptGenerator):
+    """Batches the prompt requests of several rooms that share one LM, as
+    ``content.BatchingImageGenerator`` does for their images.  All rooms of a GPU share one round
+    clock and ask for their prompt at the same moment; each calls :meth:`generate` from its own
+    worker thread.  The first caller to take the run lock becomes the leader: it waits
+    ``window_s`` for concurrent requests, takes up to ``max_batch`` of them (FIFO) into ONE
+    ``inner.generate_many`` call (one decode batch: one pass over the weights per token position
+    for all of them) and hands every room its row; the others wait on their event and lead the
+    next batch if theirs was not taken.  An exception reaches every room of the batch."""
+
+    def __init__(self, inner, max_batch: int = 8, window_s: float = 0.05) -> None:
+        self.inner = inner
+        self.max_batch = max(1, int(max_batch))
+        self.window_s = window_s
+        self._q: List[_PromptRequest] = []
+        self._qlock = threading.Lock()
+        self._run = threading.Lock()
+        self.batch_sizes: List[int] = []
+
+    def _take(self) -> List[_PromptRequest]:
+        with self._qlock:
+            batch, self._q = self._q[:self.max_batch], self._q[self.max_batch:]
+            return batch
+
+    def generate(self, seed: str, is_seed: bool) -> Optional[str]:
+        req = _PromptRequest(seed, is_seed)
+        with self._qlock:
+            self._q.append(req)
+        while not req.done.is_set():
+            if not self._run.acquire(timeout=0.005):
+                continue
+            try:
+                if req.done.is_set():
+                    break
+                if self.window_s > 0:
+                    time.sleep(self.window_s)      # let concurrent rooms join this batch
+                batch = self._take()
+                if not batch:
+                    continue
+                self.batch_sizes.append(len(batch))
+                try:
+                    outs = self.inner.generate_many([r.seed for r in batch], [r.is_seed for r in batch])
+                    for r, o in zip(batch, outs):
+                        r.result = o
+                except BaseException as e:  # noqa: BLE001 - every room of the batch sees the failure
+                    for r in batch:
+                        r.error = e
+                for r in batch:
+                    r.done.set()
+            finally:
+                self._run.release()
+        if req.error is not None:
+            raise req.error
+        return req.result
 
 
 def image_prompt(style: str, prompt: str, template: str) -> str:

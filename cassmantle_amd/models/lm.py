@@ -15,6 +15,11 @@ already hosts the diffusion pipeline (7B bf16 = 14.5 GB of the 288 GB HBM):
   sampling → position bump) reads and writes only device buffers, so it is captured ONCE as a
   hipGraph and replayed ``max_new_tokens`` times with a single host sync at the end
   (min-new-tokens is an on-device EOS bias table, sampling noise a pre-drawn table).
+* ``noise="philox"``: the sampler draws its Gumbel noise in the kernel from a per-sequence seed
+  (``ops.lm_sample_seeded``, ops/csrc/philox_gumbel.h), so there is no table to draw and upload and
+  several rooms' prompts decode as ONE batch of up to 8 rows: one pass over the weights per token
+  position for all of them (``generate_ids_batch``, buckets of 1, 2, 4, 8 rows with a captured
+  graph each).
 
 Weights are random-init by default (no checkpoints on the box); ``models/weights.py``
 ``load_causal_lm`` maps a HF-layout safetensors checkpoint in.  Without a real tokenizer a
@@ -25,8 +30,9 @@ from __future__ import annotations
 
 import math
 import threading
+import time
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -172,12 +178,55 @@ class CausalLM(nn.Module):
         return x @ self.lm_head.float().t()
 
 
+LM_NOISE = ("table", "philox")
+BUCKETS = (1, 2, 4, 8)            # batch sizes of the philox decode path, capped at max_batch
+
+
+class _Bucket:
+    """Static buffers and the captured decode graph of one batch size (``noise="philox"``)."""
+
+    def __init__(self, gen: "LMTextGenerator", B: int) -> None:
+        dev, max_new_cap = gen.device, gen.max_new_cap
+        self.B = B
+        self.kc, self.vc = gen.model.alloc_cache(B, gen.cfg.max_ctx)   # [layers, B, L, Hk, hd]
+        self.tok = torch.zeros((B,), device=dev, dtype=torch.long)
+        self.pos = torch.zeros((B,), device=dev, dtype=torch.int32)
+        self.lens = torch.ones((B,), device=dev, dtype=torch.int32)
+        self.step = torch.zeros((B,), device=dev, dtype=torch.long)
+        self.seeds = torch.zeros((B,), device=dev, dtype=torch.long)
+        self.out = torch.zeros((max_new_cap, B), device=dev, dtype=torch.long)
+        self.graph = None
+        pin = dev.type == "cuda"
+        # one pinned staging row per buffer: filled on the host, one copy each per call
+        self.h_tok = torch.zeros((B,), dtype=torch.long, pin_memory=pin)
+        self.h_pos = torch.zeros((B,), dtype=torch.int32, pin_memory=pin)
+        self.h_lens = torch.zeros((B,), dtype=torch.int32, pin_memory=pin)
+        self.h_seeds = torch.zeros((B,), dtype=torch.long, pin_memory=pin)
+
+    def state(self):
+        return self.tok, self.pos, self.lens, self.step
+
+
 class LMTextGenerator:
     """``generate_text(prompt, min_new_tokens, max_new_tokens)`` for
-    :class:`~cassmantle_amd.game.prompts.LMPromptGenerator` (continuation only, no echo)."""
+    :class:`~cassmantle_amd.game.prompts.LMPromptGenerator` (continuation only, no echo).
+
+    ``noise="table"`` (default): one batch-1 sequence per call, Gumbel noise drawn on the host and
+    uploaded as a [max_new, 1, vocab] table.  ``noise="philox"``: the sampler draws its noise in
+    the kernel from a per-sequence seed (``ops.lm_sample_seeded``), so up to ``max_batch``
+    sequences decode as one batch (``generate_ids_batch`` / ``generate_texts``), in the smallest
+    bucket of 1, 2, 4, 8 rows that holds them; a sequence's tokens depend on its prompt and seed
+    alone, not on the bucket, its row or the other sequences (given row-independent logits)."""
 
     def __init__(self, cfg: CausalLMConfig = TINY_LM, device=None, seed: int = 0, use_graphs: bool = True,
-                 tokenizer=None, temperature: float = 0.8, top_k: int = 40, max_new_cap: int = 128) -> None:
+                 tokenizer=None, temperature: float = 0.8, top_k: int = 40, max_new_cap: int = 128,
+                 noise: str = "table", max_batch: int = 1) -> None:
+        if noise not in LM_NOISE:
+            raise ValueError(f"unknown lm noise {noise!r}: one of {', '.join(LM_NOISE)}")
+        if not 1 <= int(max_batch) <= BUCKETS[-1]:
+            raise ValueError(f"max_batch must be 1..{BUCKETS[-1]}, not {max_batch}")
+        if max_batch > 1 and noise != "philox":
+            raise ValueError("max_batch > 1 needs noise='philox'")
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
         self.device = torch.device(device)
@@ -188,19 +237,29 @@ class LMTextGenerator:
         self.use_graphs = use_graphs and self.device.type == "cuda"
         self.max_new_cap = max_new_cap
         self.seed = seed
+        self.noise_mode = noise
+        self.max_batch = int(max_batch)
+        dev = self.device
+        self.eos_bias = torch.zeros((max_new_cap,), device=dev, dtype=torch.float32)
+        self.calls = 0
+        self._lock = threading.Lock()
+        self.host_ms = 0.0           # philox path: host time of the last call before its first launch
+        if noise == "philox":
+            # no noise table, no host RNG: one set of static buffers and one graph per bucket
+            self.bucket_sizes = tuple(sorted({min(b, self.max_batch) for b in BUCKETS}))
+            self.buckets: Dict[int, _Bucket] = {}
+            # a reference sampler that reads its counters on the host cannot be captured
+            self.use_graphs = self.use_graphs and ops.get_mode() == "hip"
+            return
         L = cfg.max_ctx
         self.kc, self.vc = self.model.alloc_cache(1, L)
-        dev = self.device
         self.tok_buf = torch.zeros((1,), device=dev, dtype=torch.long)
         self.pos = torch.zeros((1,), device=dev, dtype=torch.int32)
         self.lens = torch.ones((1,), device=dev, dtype=torch.int32)
         self.idx = torch.zeros((1,), device=dev, dtype=torch.long)
         self.noise = torch.zeros((max_new_cap, 1, cfg.vocab), device=dev, dtype=torch.float32)
-        self.eos_bias = torch.zeros((max_new_cap,), device=dev, dtype=torch.float32)
         self.out = torch.zeros((max_new_cap, 1), device=dev, dtype=torch.long)
         self.graph = None
-        self.calls = 0
-        self._lock = threading.Lock()
 
     # one decode step entirely on device buffers (captured as a graph on GPU)
     def _step(self) -> None:
@@ -228,6 +287,8 @@ class LMTextGenerator:
 
     @torch.no_grad()
     def generate_ids(self, prompt_ids: Sequence[int], min_new: int, max_new: int) -> List[int]:
+        if self.noise_mode == "philox":
+            return self.generate_ids_batch([prompt_ids], min_new, max_new)[0]
         max_new = max(1, min(max_new, self.max_new_cap))
         L = self.cfg.max_ctx
         ids = list(prompt_ids)[-(L - max_new):] or [self.tok.bos]
@@ -266,3 +327,98 @@ class LMTextGenerator:
         with self._lock:
             ids = self.generate_ids(self.tok.encode(prompt), min_new_tokens, max_new_tokens)
         return self.tok.decode(ids)
+
+    # ---------------------------------------------------------------- batch decode (noise="philox")
+    def _bucket(self, n: int) -> _Bucket:
+        B = next(b for b in self.bucket_sizes if b >= n)
+        if B not in self.buckets:
+            self.buckets[B] = _Bucket(self, B)
+        return self.buckets[B]
+
+    def _step_batch(self, bk: _Bucket) -> None:
+        logits = self.model(bk.tok.view(bk.B, 1), bk.kc, bk.vc, bk.pos, bk.lens, decode=True)
+        # top-k + Gumbel-max per row, the noise drawn in the kernel from the row's seed and step
+        ops.lm_sample_seeded(logits, bk.seeds, self.eos_bias, self.tok.eos, self.temperature, self.top_k, bk.step,
+                             bk.out, bk.tok, bk.pos, bk.lens)
+
+    def _capture_batch(self, bk: _Bucket) -> None:
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        saved = [t.clone() for t in bk.state()]
+        with torch.cuda.stream(s):
+            self._step_batch(bk)
+        torch.cuda.current_stream().wait_stream(s)
+        for t, v in zip(bk.state(), saved):
+            t.copy_(v)
+        g = torch.cuda.CUDAGraph()
+        with TRACER.capturing(), torch.cuda.graph(g, capture_error_mode="thread_local"):
+            self._step_batch(bk)
+        for t, v in zip(bk.state(), saved):
+            t.copy_(v)
+        bk.graph = g
+
+    @torch.no_grad()
+    def generate_ids_batch(self, prompts: Sequence[Sequence[int]], min_new: int, max_new: int,
+                           seeds: Optional[Sequence[int]] = None) -> List[List[int]]:
+        """Continuations of up to ``max_batch`` prompts decoded as one batch.  ``seeds``: one
+        64-bit seed per sequence (default ``self.seed * 1000003 + call number``, one call number
+        per sequence in request order).  Every row is cut at its first EOS."""
+        if self.noise_mode != "philox":
+            raise ValueError("generate_ids_batch needs noise='philox' (the noise table is batch 1)")
+        n = len(prompts)
+        if n == 0:
+            return []
+        if n > self.max_batch:
+            raise ValueError(f"{n} sequences exceed max_batch={self.max_batch}")
+        if seeds is not None and len(seeds) != n:
+            raise ValueError("one seed per sequence")
+        t_host = time.perf_counter()
+        bk = self._bucket(n)
+        B, dev = bk.B, self.device
+        max_new = max(1, min(max_new, self.max_new_cap))
+        L, bos = self.cfg.max_ctx, self.tok.bos
+        # spare rows hold a one-token BOS prompt and are ignored
+        rows = [list(p)[-(L - max_new):] or [bos] for p in prompts] + [[bos]] * (B - n)
+        if seeds is None:
+            seeds = [self.seed * 1000003 + self.calls + i for i in range(n)]
+        self.calls += n
+        for b, r in enumerate(rows):
+            bk.h_tok[b], bk.h_pos[b], bk.h_lens[b] = r[-1], len(r) - 1, len(r)
+            s = (int(seeds[b]) if b < n else 0) & 0xFFFFFFFFFFFFFFFF
+            bk.h_seeds[b] = s - (1 << 64) if s >= 1 << 63 else s
+        eb = torch.zeros((self.max_new_cap,))
+        eb[:min(min_new, self.max_new_cap)] = float("-inf")
+        Tmax = max(len(r) for r in rows)
+        pre = None
+        if Tmax > 1:
+            # one padded prefill: all but each row's last token, left-aligned, padded with BOS.  A valid
+            # position never attends a later (padded) one, the padded cache rows lie at or beyond
+            # lens[b] (masked by decode_attention), and decode overwrites pos[b] before lens[b] covers it
+            pre = torch.full((B, Tmax - 1), bos, dtype=torch.long)
+            for b, r in enumerate(rows):
+                pre[b, :len(r) - 1] = torch.tensor(r[:-1], dtype=torch.long)
+        self.host_ms = (time.perf_counter() - t_host) * 1e3
+        self.eos_bias.copy_(eb.to(dev))
+        bk.step.zero_()
+        bk.seeds.copy_(bk.h_seeds, non_blocking=True)
+        if pre is not None:
+            bk.pos.zero_()
+            self.model(pre.to(dev), bk.kc, bk.vc, bk.pos, None, decode=False)
+        bk.pos.copy_(bk.h_pos, non_blocking=True)
+        bk.lens.copy_(bk.h_lens, non_blocking=True)
+        bk.tok.copy_(bk.h_tok, non_blocking=True)
+        if self.use_graphs and bk.graph is None:
+            self._capture_batch(bk)
+        for _ in range(max_new):
+            if bk.graph is not None:
+                bk.graph.replay()
+            else:
+                self._step_batch(bk)
+        out = bk.out[:max_new, :n].t().tolist()       # the one sync; also orders the pinned rows' reuse
+        eos = self.tok.eos
+        return [r[:r.index(eos)] if eos in r else r for r in out]
+
+    def generate_texts(self, prompts: Sequence[str], min_new_tokens: int, max_new_tokens: int) -> List[str]:
+        with self._lock:
+            ids = self.generate_ids_batch([self.tok.encode(p) for p in prompts], min_new_tokens, max_new_tokens)
+        return [self.tok.decode(r) for r in ids]

@@ -326,6 +326,29 @@ def philox_normal(seeds, step: int, pixels) -> np.ndarray:
     return z.astype(np.float32)
 
 
+def philox_gumbel_words(seeds, step: int, ids) -> np.ndarray:
+    """The Philox word of the Gumbel contract (ops/csrc/philox_gumbel.h): uint32 [B, n] for seeds
+    [B], decode step ``step`` and vocabulary ids [n]: word ``id & 3`` of counter (id >> 2, step, 0, 0)."""
+    ids = np.asarray(ids, dtype=np.uint64).reshape(-1)
+    keys = np.asarray([seed_key(s) for s in np.asarray(seeds).reshape(-1).tolist()], dtype=np.uint64)
+    ctr = np.zeros((ids.shape[0], 4), dtype=np.uint64)
+    ctr[:, 0], ctr[:, 1] = ids >> np.uint64(2), np.uint64(int(step) & 0xFFFFFFFF)
+    w = philox4x32(ctr[None], keys.reshape(-1, 1, 2))                # [B, n, 4]
+    return np.take_along_axis(w, (ids & np.uint64(3)).astype(np.int64)[None, :, None], axis=-1)[..., 0]
+
+
+def gumbel_of_words(w) -> np.ndarray:
+    """g = -ln(-ln u), u = ((w >> 8) + 0.5) * 2^-24, in float64"""
+    u = ((np.asarray(w, dtype=np.uint32) >> np.uint32(8)).astype(np.float64) + 0.5) * 2.0 ** -24
+    return -np.log(-np.log(u))
+
+
+def philox_gumbel(seeds, step: int, ids) -> np.ndarray:
+    """The Gumbel contract's noise in float64: [B, n] for seeds [B], the sequence's decode step and
+    vocabulary ids [n].  A token's noise depends on its seed, the step and the id alone."""
+    return gumbel_of_words(philox_gumbel_words(seeds, step, ids))
+
+
 def latent_step_reference(eps, x, hist, xs, coef, step, unet_in, cfg: bool, noise_seeds=None) -> None:
     """PyTorch semantics of the fused latent-step kernel (in place).  ``noise_seeds``: int64 [B],
     needed when the row draws noise (column 15)."""

@@ -592,6 +592,30 @@ def lm_sample(logits: torch.Tensor, noise: torch.Tensor, eos_bias: torch.Tensor,
                     lens)
 
 
+def lm_sample_seeded(logits: torch.Tensor, seeds: torch.Tensor, eos_bias: torch.Tensor, eos: int,
+                     temperature: float, k: int, step: torch.Tensor, out: torch.Tensor, tok: torch.Tensor,
+                     pos: torch.Tensor, lens: torch.Tensor) -> None:
+    """One decode step's sampling for a batch of 1..8 sequences, the Gumbel noise drawn in the
+    kernel from each row's seed and own step counter (no noise table): logits [B, V] bf16 / fp32
+    (rows may be strided), seeds / step / tok [B] int64, pos / lens [B] int32, eos_bias [steps],
+    out [steps, B].  ``ops.reference.lm_sample_seeded`` is the contract; on the GPU one in-tree
+    kernel (lm_sample_seeded.hip)."""
+    if not _use_hip(logits):
+        return ref.lm_sample_seeded(logits, seeds, eos_bias, eos, temperature, k, step, out, tok, pos, lens)
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        logits = logits.reshape(-1, logits.shape[-1]).contiguous()
+    ext().lm_sample_seeded(logits, seeds, eos_bias, int(eos), float(temperature), int(k), step, out, tok, pos, lens)
+
+
+def lm_gumbel(seeds: torch.Tensor, step: int, ids: torch.Tensor) -> torch.Tensor:
+    """The seeded sampler's noise alone: g(seeds[b], step, ids[j]) as fp32 [B, n] (seeds, ids int64)."""
+    if not _use_hip(seeds):
+        return ref.lm_gumbel(seeds, step, ids)
+    out = torch.empty((seeds.numel(), ids.numel()), device=seeds.device, dtype=torch.float32)
+    ext().lm_gumbel(seeds.contiguous(), int(step) & 0xFFFFFFFF, ids.contiguous(), out)
+    return out
+
+
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, lens: torch.Tensor,
                      scale: Optional[float] = None) -> torch.Tensor:
     """One query token per sequence.  q [B, H, d]; caches [B, L, Hk, d]; lens [B] int32 (device)

@@ -849,6 +849,57 @@ void lm_sample(const at::Tensor& logits, const at::Tensor& noise, const at::Tens
                    cur_stream());
 }
 
+// batched sampler with in-kernel Gumbel noise: logits [B, V] (rows may be strided), per-row state
+void lm_sample_seeded(const at::Tensor& logits, const at::Tensor& seeds, const at::Tensor& eos_bias, int64_t eos,
+                      double temperature, int64_t k, at::Tensor& step, at::Tensor& out, at::Tensor& tok,
+                      at::Tensor& pos, at::Tensor& lens) {
+  CHECK_DEV(logits); CHECK_DEV(seeds); CHECK_DEV(eos_bias); CHECK_DEV(step); CHECK_DEV(out); CHECK_DEV(tok);
+  CHECK_DEV(pos); CHECK_DEV(lens);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1),
+              "lm_sample_seeded: logits [B, V] with contiguous rows");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(B >= 1 && B <= 8 && V >= 1 && V < (int64_t(1) << 31), "lm_sample_seeded: 1 <= B <= 8, 1 <= V < 2^31");
+  TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16,
+              "lm_sample_seeded: f32 / bf16 logits");
+  CHECK_CONTIG(seeds); CHECK_CONTIG(eos_bias); CHECK_CONTIG(step); CHECK_CONTIG(out); CHECK_CONTIG(tok);
+  CHECK_CONTIG(pos); CHECK_CONTIG(lens);
+  TORCH_CHECK(seeds.scalar_type() == at::kLong && seeds.numel() == B, "lm_sample_seeded: seeds [B] int64");
+  TORCH_CHECK(eos_bias.scalar_type() == at::kFloat && eos_bias.numel() >= 1, "lm_sample_seeded: eos_bias [steps] f32");
+  const int64_t steps = eos_bias.numel();
+  TORCH_CHECK(steps < (int64_t(1) << 31), "lm_sample_seeded: too many steps");
+  TORCH_CHECK(out.scalar_type() == at::kLong && out.numel() == steps * B, "lm_sample_seeded: out [steps, B] int64");
+  TORCH_CHECK(step.scalar_type() == at::kLong && tok.scalar_type() == at::kLong && step.numel() == B && tok.numel() == B,
+              "lm_sample_seeded: step / token [B] int64");
+  TORCH_CHECK(pos.scalar_type() == at::kInt && lens.scalar_type() == at::kInt && pos.numel() == B && lens.numel() == B,
+              "lm_sample_seeded: pos / lens [B] int32");
+  TORCH_CHECK(k >= 1 && temperature > 0, "lm_sample_seeded: k >= 1, temperature > 0");
+  LmSampleSeededArgs a;
+  a.logits = logits.data_ptr(); a.ld = logits.stride(0);
+  a.seeds = reinterpret_cast<const long long*>(seeds.data_ptr<int64_t>());
+  a.eos_bias = eos_bias.data_ptr<float>();
+  a.step = reinterpret_cast<long long*>(step.data_ptr<int64_t>());
+  a.out = reinterpret_cast<long long*>(out.data_ptr<int64_t>());
+  a.tok = reinterpret_cast<long long*>(tok.data_ptr<int64_t>());
+  a.pos = pos.data_ptr<int>(); a.lens = lens.data_ptr<int>();
+  a.B = (int)B; a.V = (int)V; a.k = (int)std::min<int64_t>(k, V);
+  a.eos = (eos >= 0 && eos < V) ? (int)eos : -1;   // an eos outside the vocabulary biases nothing
+  a.steps = (int)steps; a.temp = (float)temperature;
+  launch_lm_sample_seeded(a, logits.scalar_type() == at::kFloat, cur_stream());
+}
+
+// the sampler's noise alone: out[b, j] = g(seeds[b], step, ids[j])
+void lm_gumbel(const at::Tensor& seeds, int64_t step, const at::Tensor& ids, at::Tensor& out) {
+  CHECK_DEV(seeds); CHECK_DEV(ids); CHECK_DEV(out); CHECK_CONTIG(seeds); CHECK_CONTIG(ids); CHECK_CONTIG(out);
+  TORCH_CHECK(seeds.scalar_type() == at::kLong && seeds.dim() == 1, "lm_gumbel: seeds [B] int64");
+  TORCH_CHECK(ids.scalar_type() == at::kLong && ids.dim() == 1, "lm_gumbel: ids [n] int64");
+  TORCH_CHECK(ids.numel() < (int64_t(1) << 31) && seeds.numel() < (int64_t(1) << 31), "lm_gumbel: too many ids");
+  TORCH_CHECK(out.scalar_type() == at::kFloat && out.dim() == 2 && out.size(0) == seeds.numel() &&
+              out.size(1) == ids.numel(), "lm_gumbel: out [B, n] f32");
+  launch_lm_gumbel(reinterpret_cast<const long long*>(seeds.data_ptr<int64_t>()), (unsigned)(uint64_t)step,
+                   reinterpret_cast<const long long*>(ids.data_ptr<int64_t>()), (int)ids.numel(), (int)seeds.numel(),
+                   out.data_ptr<float>(), cur_stream());
+}
+
 void decode_attention(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
                       const at::Tensor& lens, at::Tensor& out, double scale) {
   CHECK_DEV(q); CHECK_BF16(q); CHECK_BF16(k_cache); CHECK_CONTIG(k_cache); CHECK_CONTIG(v_cache);
@@ -1230,6 +1281,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("zero_", &zero_, nogil());
   m.def("prefetch", &prefetch, nogil());
   m.def("lm_sample", &lm_sample, nogil());
+  m.def("lm_sample_seeded", &lm_sample_seeded, nogil());
+  m.def("lm_gumbel", &lm_gumbel, nogil());
   m.def("cu_mask_stream", &cu_mask_stream);
   m.def("cu_count", &cu_count);
   m.def("softmax_rows", &softmax_rows, nogil());

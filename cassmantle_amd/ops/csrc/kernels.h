@@ -172,6 +172,23 @@ void launch_lm_sample(const void* logits, int logits_f32, int V, const float* no
                       float temperature, int k, long long* step, long long* out, long long* tok, int* pos, int* lens,
                       hipStream_t s);
 void launch_decode_attention(const DecodeArgs& a, int ns, hipStream_t s);
+// batched decode-step sampler, Gumbel noise drawn in the kernel (lm_sample_seeded.hip, the GUMBEL
+// CONTRACT of philox_gumbel.h): one workgroup per row, every row with its own seed and step counter
+struct LmSampleSeededArgs {
+  const void* logits; long long ld;    // [B][V] bf16 / fp32, row stride in elements
+  const long long* seeds;              // [B] 64-bit sequence seeds
+  const float* eos_bias;               // [steps]
+  long long* step;                     // [B] per-row step counters
+  long long* out;                      // [steps][B]
+  long long* tok;                      // [B]
+  int* pos; int* lens;                 // [B]
+  int B, V, k, eos, steps;
+  float temp;
+};
+void launch_lm_sample_seeded(const LmSampleSeededArgs& a, int logits_f32, hipStream_t s);
+// out[b][j] = g(seeds[b], step, ids[j]) fp32
+void launch_lm_gumbel(const long long* seeds, unsigned step, const long long* ids, int n, int B, float* out,
+                      hipStream_t s);
 
 // scorer
 void launch_gather_cosine(const void* table, int table_f32, int D, const int* ia, const int* ib,

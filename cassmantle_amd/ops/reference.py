@@ -294,3 +294,38 @@ def lm_sample(logits, noise, eos_bias, eos: int, temperature: float, k: int, ste
     pos.add_(1)
     lens.add_(1)
     step.add_(1)
+
+
+def lm_gumbel(seeds, step: int, ids) -> torch.Tensor:
+    """The sampler's noise alone (GUMBEL CONTRACT, ops/csrc/philox_gumbel.h): fp32 [B, n] of the
+    float64 model ``schedulers.philox_gumbel`` for seeds [B] int64, a decode step and ids [n]."""
+    from ..models.schedulers import philox_gumbel
+    g = philox_gumbel(seeds.detach().cpu().numpy(), int(step), ids.detach().cpu().numpy())
+    return torch.from_numpy(g).to(device=seeds.device, dtype=torch.float32)
+
+
+def lm_sample_seeded(logits, seeds, eos_bias, eos: int, temperature: float, k: int, step, out, tok, pos, lens) -> None:
+    """Batched decode-step sampler with seeded noise (the contract of lm_sample_seeded_kernel), per
+    row b of logits [B, V]: v = logits / T with eos_bias[step[b]] added at ``eos``; the k largest
+    v by ``lm_sample``'s stable sort (ties keep the LOWER id); among them the id maximising
+    v + g(seeds[b], step[b], id) with the float64 model noise (first in that order on ties: the
+    larger v, then the lower id); then out[step[b], b] = tok[b] = id and pos[b], lens[b], step[b]
+    advance by one.  Every row has its own step counter and seed, and a row's token does not
+    depend on the other rows.  Reads the counters on the host: not graph-capturable."""
+    from ..models.schedulers import philox_gumbel
+    lg = logits.float() / temperature
+    B, V = lg.shape
+    steps, sds = step.tolist(), seeds.tolist()
+    for b in range(B):
+        v = lg[b:b + 1].clone()
+        if 0 <= eos < V:
+            v[:, eos] += eos_bias[steps[b]]
+        srt = torch.sort(v, dim=-1, descending=True, stable=True)
+        vals, ids = srt.values[0, :k].cpu(), srt.indices[0, :k].cpu()
+        g = philox_gumbel([sds[b]], steps[b], ids.numpy())[0]
+        nxt = int(ids[int((vals.double().numpy() + g).argmax())])
+        out[steps[b], b] = nxt
+        tok[b] = nxt
+    pos.add_(1)
+    lens.add_(1)
+    step.add_(1)

@@ -273,15 +273,27 @@ def build_prompt_generator(cfg: Config, device: Optional[str] = None):
     (HF text-generation endpoint, reference parity).  ``None`` -> per-room synthetic."""
     m = cfg.model
     if m.prompt_generator == "lm":
-        from ..game.prompts import LMPromptGenerator
-        from ..models.lm import LM_CONFIGS, LMTextGenerator, SentencePieceTokenizer
+        from ..game.prompts import BatchingPromptGenerator, LMPromptGenerator
+        from ..models.lm import LM_CONFIGS, LM_NOISE, LMTextGenerator, SentencePieceTokenizer
+        # bad LM flags raise here, not at the first round
+        if m.lm_noise not in LM_NOISE:
+            raise ValueError(f"unknown lm_noise {m.lm_noise!r}: one of {', '.join(LM_NOISE)}")
+        if not 1 <= int(m.lm_batch_max) <= 8:
+            raise ValueError(f"lm_batch_max must be 1..8, not {m.lm_batch_max}")
+        if m.lm_batch_max > 1 and m.lm_noise != "philox":
+            raise ValueError("lm_batch_max > 1 needs lm_noise=philox (the noise table is batch 1)")
         tok = SentencePieceTokenizer(m.lm_tokenizer) if m.lm_tokenizer else None
         gen = LMTextGenerator(LM_CONFIGS[m.lm_model], device=device, seed=m.seed, use_graphs=m.use_graphs,
-                              tokenizer=tok)
+                              tokenizer=tok, noise=m.lm_noise, max_batch=int(m.lm_batch_max))
         if m.lm_weights:
             from ..models.weights import load_causal_lm, read_safetensors
             load_causal_lm(gen.model, read_safetensors(m.lm_weights))
-        return LMPromptGenerator(gen)
+        pg = LMPromptGenerator(gen)
+        if m.lm_batch_max > 1:
+            # the rooms of this process ask at the same moment of the shared round clock: one LM batch
+            return BatchingPromptGenerator(pg, max_batch=int(m.lm_batch_max),
+                                           window_s=m.lm_batch_window_ms / 1e3 if cfg.game.num_rooms > 1 else 0.0)
+        return pg
     if m.prompt_generator == "remote":
         if not m.remote_prompt_url:
             raise ValueError("prompt_generator=remote needs remote_prompt_url")

@@ -1,0 +1,326 @@
+"""The batched, seeded LM sampler on the GPU (lm_sample_seeded.hip) and LMTextGenerator's batch
+decode on tiny-lm.
+
+The sampler is held to the float64 model of its contract (ops.reference.lm_sample_seeded: the
+stable sort of the fp32 v, then schedulers.philox_gumbel in float64).  The kernel adds v + g in
+fp32 with the device's logf, so a token must equal the model's choice unless the model's two best
+scores are closer than MARGIN = 1e-4 >= 2 * (17.33 * 2e-6 + 2^-18): twice the noise tolerance at
+the largest |g| plus half an ulp of a score below 32.  There the runner-up is accepted too and the
+case counts as undecided; at most 1 % of a family's cases may be.  Everything that does not pass
+through that one fp32 sum is exact: the state update, the independence of a row from its batch,
+graph replay, and the generator's results."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import kernel_oracle as ko
+from cassmantle_amd import ops
+from cassmantle_amd.models import schedulers as S
+from cassmantle_amd.models.lm import TINY_LM, ByteTokenizer, LMTextGenerator
+from cassmantle_amd.ops import reference as ref
+from cassmantle_amd.ops._ext import ext_available, ext_error
+from test_lm_gumbel_native import GUMBEL_TOL, IDS
+from test_lm_gumbel_native import SEEDS as GRID_SEEDS
+from test_lm_gumbel_native import STEPS as GRID_STEPS
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+BF16 = torch.bfloat16
+MARGIN = 1e-4
+UNDECIDED_CAP = 0.01
+SEEDS = [-1, 2 ** 63 - 1, 0x1234_5678_9ABC_DEF0, 0, 1, -2 ** 63, 42, 7 ** 20]
+
+
+@pytest.fixture(autouse=True, scope="module")
+def _ext_loaded():
+    assert ext_available(), ext_error()
+    ops.set_mode("hip")
+
+
+def model_choice(row, T, k, eos, eb, seed, step):
+    """the float64 model on one row of logits (already in the logits dtype): the winner, the
+    runner-up (or None) and the gap between their scores"""
+    v = ko.sample_values(row, T, eos, eb)
+    order = torch.sort(v, descending=True, stable=True).indices[:k]
+    sc = v[order].double().numpy() + S.philox_gumbel([seed], step, order.numpy())[0]
+    best = np.argsort(-sc, kind="stable")[:2]
+    if len(best) == 1 or not math.isfinite(sc[best[1]]):
+        return int(order[best[0]]), None, math.inf
+    return int(order[best[0]]), int(order[best[1]]), float(sc[best[0]] - sc[best[1]])
+
+
+class State:
+    """out, tok, pos, lens and step of B rows, each between canaries"""
+
+    def __init__(self, B, steps, step0):
+        self.out = ko.guarded((steps, B), torch.int64, device=DEV)
+        self.tok = ko.guarded((B,), torch.int64, device=DEV)
+        self.step = ko.guarded((B,), torch.int64, device=DEV)
+        self.pos = ko.guarded((B,), torch.int32, device=DEV)
+        self.lens = ko.guarded((B,), torch.int32, device=DEV)
+        self.out.view.fill_(-1)
+        self.tok.view.fill_(-1)
+        self.step.view.copy_(torch.as_tensor(step0, dtype=torch.long).expand(B))
+        self.pos.view.copy_(torch.arange(B, dtype=torch.int32) * 3)
+        self.lens.view.copy_(torch.arange(B, dtype=torch.int32) * 3 + 1)
+
+    def args(self):
+        return dict(step=self.step.view, out=self.out.view, tok=self.tok.view, pos=self.pos.view, lens=self.lens.view)
+
+    def read(self):
+        torch.cuda.synchronize()
+        ko.check_guards(self.out, self.tok, self.step, self.pos, self.lens)
+        return (self.out.view.cpu(), self.tok.view.tolist(), self.pos.view.tolist(), self.lens.view.tolist(),
+                self.step.view.tolist())
+
+
+def seeds_dev(seeds):
+    return torch.tensor(S.seeds_int64(seeds), device=DEV)
+
+
+def run_once(lg, seeds, T, k, eos, eb, step0, steps=96, strided=True):
+    """one launch on logits [B, V] inside a NaN buffer (padded row stride): (tokens, state)"""
+    B = lg.shape[0]
+    st = State(B, steps, step0)
+    lgp = ko.poisoned(lg, strided=strided, device=DEV)
+    assert not strided or B == 1 or lgp.stride(0) > lg.shape[1]
+    ops.lm_sample_seeded(lgp, seeds_dev(seeds), torch.full((steps,), float(eb), device=DEV), eos, T, k, **st.args())
+    out, tok, pos, lens, step = st.read()
+    s0 = torch.as_tensor(step0).expand(B).tolist()
+    assert pos == [3 * b + 1 for b in range(B)] and lens == [3 * b + 2 for b in range(B)]
+    assert step == [s + 1 for s in s0]
+    for b in range(B):
+        assert int(out[s0[b], b]) == tok[b]
+    assert int((out != -1).sum()) == B                        # every row wrote its own entry only
+    return tok
+
+
+# ------------------------------------------------------------------------------ sampler vs model
+def test_sampler_matches_the_float64_model_on_single_steps():
+    cases = undecided = 0
+    smallest = math.inf
+    for V in (300, 1025, 4097, 32000):
+        for dtype in (BF16, torch.float32):
+            for B in (1, 3, 8):
+                lg = ko.rnd(B, V, scale=3.0, seed=V + B, dtype=dtype)
+                for k in (1, 2, 40, min(V, 1000)):
+                    for step in (0, 1, 95):
+                        seeds = [SEEDS[(b + step + k) % len(SEEDS)] for b in range(B)]
+                        tok = run_once(lg, seeds, 0.8, k, 7, 0.0, step)
+                        for b in range(B):
+                            win, second, gap = model_choice(lg[b], 0.8, k, 7, 0.0, seeds[b], step)
+                            cases += 1
+                            smallest = min(smallest, gap)
+                            if gap < MARGIN:
+                                undecided += 1
+                                assert tok[b] in (win, second), (V, dtype, B, k, step, b, tok[b], win, second, gap)
+                            else:
+                                assert tok[b] == win, (V, dtype, B, k, step, b, tok[b], win, second, gap)
+    print(f"seeded sampler: {cases} cases, {undecided} undecided, smallest top-two gap {smallest:.3e}")
+    assert undecided <= UNDECIDED_CAP * cases
+
+
+def test_lm_gumbel_matches_the_model_on_the_host_programs_grid():
+    ids = torch.tensor(IDS, device=DEV)
+    worst = 0.0
+    for step in GRID_STEPS:
+        got = ops.lm_gumbel(seeds_dev(GRID_SEEDS), step, ids).cpu().double().numpy()
+        want = S.philox_gumbel(GRID_SEEDS, step, IDS)
+        err = np.abs(got - want) / np.maximum(1.0, np.abs(want))
+        worst = max(worst, float(err.max()))
+        assert np.all(err <= GUMBEL_TOL), (step, float(err.max()))
+    print(f"lm_gumbel: worst |g - model| / max(1, |g|) = {worst:.3e} (bound {GUMBEL_TOL:g})")
+    assert torch.equal(ref.lm_gumbel(seeds_dev(GRID_SEEDS).cpu(), 95, ids.cpu()),
+                       torch.from_numpy(S.philox_gumbel(GRID_SEEDS, 95, IDS)).float())
+
+
+# ------------------------------------------------------------------------------ exact properties
+@pytest.mark.parametrize("dtype", [BF16, torch.float32], ids=["bf16", "fp32"])
+def test_a_row_is_bit_identical_alone_and_in_every_slot(dtype):
+    V, k, step, seed = 4097, 40, 5, SEEDS[2]
+    row = ko.rnd(1, V, scale=3.0, seed=1, dtype=dtype)
+    alone = run_once(row, [seed], 0.8, k, 7, -2.0, step)[0]
+    for B in (3, 8):
+        for slot in range(B):
+            lg = ko.rnd(B, V, scale=3.0, seed=100 + 8 * B + slot, dtype=dtype)     # other rows change every time
+            lg[slot] = row[0]
+            seeds = [SEEDS[(b + slot) % len(SEEDS)] + 1 for b in range(B)]
+            seeds[slot] = seed
+            step0 = [(step + 1 + b) % 96 for b in range(B)]
+            step0[slot] = step
+            assert run_once(lg, seeds, 0.8, k, 7, -2.0, torch.tensor(step0))[slot] == alone, (B, slot)
+
+
+def test_contiguous_and_strided_logits_agree_and_a_finished_row_is_left_alone():
+    lg = ko.rnd(3, 1025, scale=3.0, seed=5)
+    a = run_once(lg, SEEDS[:3], 0.8, 40, 7, 0.0, 2, strided=True)
+    assert a == run_once(lg, SEEDS[:3], 0.8, 40, 7, 0.0, 2, strided=False)
+    # a row whose counter is past the table neither reads eos_bias nor writes: the others go on
+    st = State(3, 4, torch.tensor([0, 4, 3]))
+    ops.lm_sample_seeded(ko.poisoned(lg, device=DEV), seeds_dev(SEEDS[:3]), torch.zeros(4, device=DEV), 7, 0.8, 40,
+                         **st.args())
+    out, tok, pos, lens, step = st.read()
+    assert step == [1, 4, 4] and tok[1] == -1 and pos == [1, 3, 7] and lens == [2, 4, 8]
+    assert int((out != -1).sum()) == 2
+
+
+# ------------------------------------------------------------------------------ rank probes
+def _gumbel_grid(seed, steps, ids):
+    """float64 noise [steps, ids] of one seed (the model, vectorised over the steps)"""
+    ids = np.asarray(ids, dtype=np.uint64)
+    ctr = np.zeros((len(steps), len(ids), 4), dtype=np.uint64)
+    ctr[..., 0], ctr[..., 1] = (ids >> np.uint64(2))[None, :], np.asarray(steps, dtype=np.uint64)[:, None]
+    w = S.philox4x32(ctr, np.asarray(S.seed_key(seed), dtype=np.uint64))
+    w = np.take_along_axis(w, np.broadcast_to((ids & np.uint64(3)).astype(np.int64)[None, :, None], w.shape[:2] + (1,)), -1)
+    return S.gumbel_of_words(w[..., 0])
+
+
+# steps of seed SEEDS[0], found by a longer search of the model, at which the boundary ids of the two
+# large tie cases win (a tied id wins there about once in 1e4 steps); the test classifies them again
+PROBE_STEPS = {"equal-k1500": [561, 744, 1321, 1473, 3797, 4448],
+               "tie-across-chunks": [5166, 6798, 7607, 8582, 8616, 13380, 17505, 19678, 29775, 37320, 44650]}
+
+
+@pytest.mark.parametrize("T", [1.0, 0.8])
+@pytest.mark.parametrize("dtype", [BF16, torch.float32], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("c", ko.SAMPLER_CASES, ids=lambda c: c.name)
+def test_lm_sample_seeded_rank_probes(c, dtype, T):
+    """The cases of test_lm_sample_rank_probes (ties at the k-th value within and across chunks of
+    1024 ids, -0.0 next to +0.0, -inf members, the EOS bias, k > V).  The noise cannot be planted
+    here, so the probes are found instead: 8 rows (seeds) chained over 8 steps must equal the model
+    with the margin rule, and a search of the model over (seed, step) finds steps at which the id
+    ranked k - 1 or k wins (inside: the kernel must pick it) and steps at which the id ranked
+    k + 1 would win if it were admitted (outside: the kernel must pick the model's choice among
+    the first k instead).  The search has a fixed budget; what it found is printed."""
+    lg1 = c.logits.to(dtype)
+    V = lg1.numel()
+    kk = min(c.k, V)
+    lg = lg1.reshape(1, V).repeat(8, 1)
+    seeds = SEEDS[:8]
+    # ---- chained steps on the device counters, all state equal to the reference's
+    n = 8
+    st = State(8, n, 0)
+    lgp, sd, eb = ko.poisoned(lg, strided=True, device=DEV), seeds_dev(seeds), torch.full((n,), c.eos_bias, device=DEV)
+    for _ in range(n):
+        ops.lm_sample_seeded(lgp, sd, eb, c.eos, T, c.k, **st.args())
+    out, tok, pos, lens, step = st.read()
+    assert step == [n] * 8 and pos == [3 * b + n for b in range(8)] and lens == [3 * b + 1 + n for b in range(8)]
+    assert tok == out[n - 1].tolist()
+    undecided = 0
+    for s in range(n):
+        for b in range(8):
+            win, second, gap = model_choice(lg1, T, c.k, c.eos, c.eos_bias, seeds[b], s)
+            undecided += gap < MARGIN
+            assert int(out[s, b]) == win or (gap < MARGIN and int(out[s, b]) == second), (c.name, s, b, win, gap)
+    assert undecided <= UNDECIDED_CAP * 8 * n
+    # ---- boundary probes found by the model
+    v = ko.sample_values(lg1, T, c.eos, c.eos_bias)
+    order = torch.sort(v, descending=True, stable=True).indices[:kk + 1]
+    vals = v[order].double().numpy()
+    N = int(min(4096, max(64, 300000 // (kk + 1))))
+    found = []                                                  # (seed, step, want, kind)
+    for seed in seeds[:2]:
+        steps = np.arange(N)
+        if seed == seeds[0]:
+            steps = np.concatenate([steps, np.asarray(PROBE_STEPS.get(c.name, []), dtype=np.int64)])
+        sc = vals[None, :] + _gumbel_grid(seed, steps, order.numpy())
+        top2 = np.sort(sc[:, :kk], axis=1)[:, -2:] if kk > 1 else None
+        clear = np.ones(len(steps), bool) if top2 is None else (top2[:, 1] - top2[:, 0] >= MARGIN)
+        win_k = sc[:, :kk].argmax(1)
+        for r in (kk - 1, kk):                                  # 1-based ranks inside the set
+            hits = np.nonzero((win_k == r - 1) & clear)[0] if r >= 1 else []
+            found += [(seed, int(steps[j]), int(order[r - 1]), f"inside-{r}") for j in hits[:2]]
+        if kk < V and math.isfinite(vals[kk]):
+            hits = np.nonzero((sc.argmax(1) == kk) & clear)[0]  # the id ranked k + 1 beats the whole set
+            found += [(seed, int(steps[j]), int(order[win_k[j]]), "outside") for j in hits[:2]]
+    print(f"seeded probes {c.name} {dtype} T={T}: {[(f[3], f[1]) for f in found]} of {N} steps x 2 seeds")
+    if c.name in PROBE_STEPS or kk < min(V, 64):
+        assert {"outside", f"inside-{kk}"} <= {f[3] for f in found}, "the search lost its boundary probes"
+    table = max([N] + [f[1] + 1 for f in found])
+    for i in range(0, len(found), 8):
+        grp = found[i:i + 8]
+        tokens = run_once(lg[:len(grp)], [f[0] for f in grp], T, c.k, c.eos, c.eos_bias,
+                          torch.tensor([f[1] for f in grp]), steps=table)
+        assert tokens == [f[2] for f in grp], (c.name, grp, tokens)
+
+
+# ------------------------------------------------------------------------------ graph and stream
+@pytest.mark.parametrize("side_stream", [False, True], ids=["default-stream", "side-stream"])
+def test_graph_replay_of_eight_steps_equals_the_eager_loop(side_stream):
+    B, V, n = 3, 1025, 8
+    lg = ko.rnd(B, V, scale=3.0, seed=9).to(DEV)
+    sd, eb = seeds_dev(SEEDS[:B]), torch.zeros(n, device=DEV)
+
+    def fresh():
+        return dict(step=torch.zeros(B, device=DEV, dtype=torch.long), out=torch.full((n, B), -1, device=DEV),
+                    tok=torch.zeros(B, device=DEV, dtype=torch.long), pos=torch.zeros(B, device=DEV, dtype=torch.int32),
+                    lens=torch.ones(B, device=DEV, dtype=torch.int32))
+
+    eager = fresh()
+    for _ in range(n):
+        ops.lm_sample_seeded(lg, sd, eb, 7, 0.8, 40, **eager)
+    torch.cuda.synchronize()
+    st = fresh()
+    stream = torch.cuda.Stream() if side_stream else torch.cuda.current_stream()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(stream):
+        with torch.cuda.graph(g, stream=stream if side_stream else None):
+            ops.lm_sample_seeded(lg, sd, eb, 7, 0.8, 40, **st)
+        for _ in range(n):
+            g.replay()
+    stream.synchronize()
+    torch.cuda.synchronize()
+    for name in eager:
+        assert torch.equal(eager[name], st[name]), name
+    assert st["step"].tolist() == [n] * B and int((st["out"] < 0).sum()) == 0
+
+
+# ------------------------------------------------------------------------------ generator on tiny-lm
+TOK = ByteTokenizer()
+PROMPTS = [TOK.encode(t) for t in ("The silver dunes", "A fox waited here", "In the old harbor", "Beneath a lantern.")]
+PSEEDS = [11, 12, 13, 14]
+
+
+@pytest.fixture(scope="module")
+def gens():
+    return {g: LMTextGenerator(TINY_LM, device=DEV, seed=0, use_graphs=g, noise="philox", max_batch=8)
+            for g in (True, False)}
+
+
+def test_generator_graphs_on_equals_graphs_off_and_repeats(gens):
+    assert len({len(p) for p in PROMPTS}) > 1                  # the padded prefill has rows to pad
+    a = gens[True].generate_ids_batch(PROMPTS[:3], 4, 16, seeds=PSEEDS[:3])
+    assert gens[True].buckets[4].graph is not None and gens[False].buckets.get(4) is None
+    assert a == gens[False].generate_ids_batch(PROMPTS[:3], 4, 16, seeds=PSEEDS[:3])
+    assert a == gens[True].generate_ids_batch(PROMPTS[:3], 4, 16, seeds=PSEEDS[:3])     # same seeds twice
+    assert all(4 <= len(r) <= 16 for r in a)
+    assert a != gens[True].generate_ids_batch(PROMPTS[:3], 4, 16, seeds=[21, 22, 23])
+    assert gens[True].generate_ids(PROMPTS[0], 4, 16) is not None and 1 in gens[True].buckets
+
+
+def test_a_permutation_of_the_prompts_permutes_the_results(gens):
+    a = gens[True].generate_ids_batch(PROMPTS, 4, 16, seeds=PSEEDS)
+    perm = [2, 0, 3, 1]
+    b = gens[True].generate_ids_batch([PROMPTS[i] for i in perm], 4, 16, seeds=[PSEEDS[i] for i in perm])
+    assert b == [a[i] for i in perm]
+
+
+def test_three_prompts_in_bucket_four_do_not_see_the_spare_row(gens):
+    a = gens[True].generate_ids_batch(PROMPTS[:3], 4, 16, seeds=PSEEDS[:3])
+    b = gens[True].generate_ids_batch(PROMPTS[:3] + [TOK.encode("Other words")], 4, 16, seeds=PSEEDS[:3] + [99])
+    assert b[:3] == a
+
+
+def test_alone_equals_bucket_eight_through_the_gemv(gens):
+    """two-token prompts: prefill (one position) and decode both run the skinny-M GEMV, which sums
+    every row by the same lane butterfly and k order whatever M, so a sequence alone (M = 1) and
+    in a bucket of 8 (M = 8) gives the same tokens bit for bit"""
+    prompts = [[TOK.bos, 65 + i] for i in range(8)]
+    seeds = list(range(31, 39))
+    batch = gens[True].generate_ids_batch(prompts, 4, 16, seeds=seeds)
+    assert sorted(gens[True].buckets)[-1] == 8
+    for i in (0, 3, 7):
+        assert gens[True].generate_ids_batch([prompts[i]], 4, 16, seeds=[seeds[i]])[0] == batch[i], i
