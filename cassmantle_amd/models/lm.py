@@ -183,11 +183,15 @@ BUCKETS = (1, 2, 4, 8)            # batch sizes of the philox decode path, cappe
 
 
 class _Bucket:
-    """Static buffers and the captured decode graph of one batch size (``noise="philox"``)."""
+    """Static buffers and the captured decode graph of one batch size.  ``noise="table"`` has the
+    one-row bucket only, which also owns the [max_new_cap, 1, vocab] noise table."""
 
     def __init__(self, gen: "LMTextGenerator", B: int) -> None:
         dev, max_new_cap = gen.device, gen.max_new_cap
         self.B = B
+        self.noise = None
+        if gen.noise_mode == "table":
+            self.noise = torch.zeros((max_new_cap, 1, gen.cfg.vocab), device=dev, dtype=torch.float32)
         self.kc, self.vc = gen.model.alloc_cache(B, gen.cfg.max_ctx)   # [layers, B, L, Hk, hd]
         self.tok = torch.zeros((B,), device=dev, dtype=torch.long)
         self.pos = torch.zeros((B,), device=dev, dtype=torch.int32)
@@ -216,7 +220,8 @@ class LMTextGenerator:
     the kernel from a per-sequence seed (``ops.lm_sample_seeded``), so up to ``max_batch``
     sequences decode as one batch (``generate_ids_batch`` / ``generate_texts``), in the smallest
     bucket of 1, 2, 4, 8 rows that holds them; a sequence's tokens depend on its prompt and seed
-    alone, not on the bucket, its row or the other sequences (given row-independent logits)."""
+    alone, not on the bucket, its row or the other sequences (given row-independent logits).  Both
+    modes run one decode loop (``_decode``) over a bucket; the table path is its one-row case."""
 
     def __init__(self, cfg: CausalLMConfig = TINY_LM, device=None, seed: int = 0, use_graphs: bool = True,
                  tokenizer=None, temperature: float = 0.8, top_k: int = 40, max_new_cap: int = 128,
@@ -243,119 +248,63 @@ class LMTextGenerator:
         self.eos_bias = torch.zeros((max_new_cap,), device=dev, dtype=torch.float32)
         self.calls = 0
         self._lock = threading.Lock()
-        self.host_ms = 0.0           # philox path: host time of the last call before its first launch
+        # host time of the last call before its first launch (table path: the table drawn and uploaded too)
+        self.host_ms = 0.0
+        # one set of static buffers and one graph per bucket, made when first used
+        self.bucket_sizes = tuple(sorted({min(b, self.max_batch) for b in BUCKETS}))
+        self.buckets: Dict[int, _Bucket] = {}
         if noise == "philox":
-            # no noise table, no host RNG: one set of static buffers and one graph per bucket
-            self.bucket_sizes = tuple(sorted({min(b, self.max_batch) for b in BUCKETS}))
-            self.buckets: Dict[int, _Bucket] = {}
             # a reference sampler that reads its counters on the host cannot be captured
             self.use_graphs = self.use_graphs and ops.get_mode() == "hip"
-            return
-        L = cfg.max_ctx
-        self.kc, self.vc = self.model.alloc_cache(1, L)
-        self.tok_buf = torch.zeros((1,), device=dev, dtype=torch.long)
-        self.pos = torch.zeros((1,), device=dev, dtype=torch.int32)
-        self.lens = torch.ones((1,), device=dev, dtype=torch.int32)
-        self.idx = torch.zeros((1,), device=dev, dtype=torch.long)
-        self.noise = torch.zeros((max_new_cap, 1, cfg.vocab), device=dev, dtype=torch.float32)
-        self.out = torch.zeros((max_new_cap, 1), device=dev, dtype=torch.long)
-        self.graph = None
 
-    # one decode step entirely on device buffers (captured as a graph on GPU)
-    def _step(self) -> None:
-        logits = self.model(self.tok_buf.view(1, 1), self.kc, self.vc, self.pos, self.lens, decode=True)
-        # top-k + Gumbel-max with this step's noise row, and the token / position / length / step
-        # update: one in-tree kernel on the GPU (lm.hip lm_sample_kernel), no ATen sampling ops
-        ops.lm_sample(logits, self.noise, self.eos_bias, self.tok.eos, self.temperature, self.top_k, self.idx,
-                      self.out, self.tok_buf, self.pos, self.lens)
-
-    def _capture(self) -> None:
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        saved = [t.clone() for t in (self.tok_buf, self.pos, self.lens, self.idx)]
-        with torch.cuda.stream(s):
-            self._step()
-        torch.cuda.current_stream().wait_stream(s)
-        for t, v in zip((self.tok_buf, self.pos, self.lens, self.idx), saved):
-            t.copy_(v)
-        g = torch.cuda.CUDAGraph()
-        with TRACER.capturing(), torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._step()
-        for t, v in zip((self.tok_buf, self.pos, self.lens, self.idx), saved):
-            t.copy_(v)
-        self.graph = g
-
-    @torch.no_grad()
-    def generate_ids(self, prompt_ids: Sequence[int], min_new: int, max_new: int) -> List[int]:
-        if self.noise_mode == "philox":
-            return self.generate_ids_batch([prompt_ids], min_new, max_new)[0]
-        max_new = max(1, min(max_new, self.max_new_cap))
-        L = self.cfg.max_ctx
-        ids = list(prompt_ids)[-(L - max_new):] or [self.tok.bos]
-        dev = self.device
-        T = len(ids)
-        gen = torch.Generator(device="cpu").manual_seed(self.seed * 1000003 + self.calls)
-        self.calls += 1
-        u = torch.rand((max_new, 1, self.cfg.vocab), generator=gen).clamp_(1e-10, 1.0 - 1e-7)
-        self.noise[:max_new].copy_((-torch.log(-torch.log(u))).to(dev))
-        eb = torch.zeros((self.max_new_cap,))
-        eb[:min(min_new, self.max_new_cap)] = float("-inf")
-        self.eos_bias.copy_(eb.to(dev))
-        self.idx.zero_()
-        # prefill all but the last prompt token; the decode step consumes the last one
-        self.pos.zero_()
-        if T > 1:
-            pre = torch.tensor([ids[:-1]], device=dev, dtype=torch.long)
-            self.model(pre, self.kc, self.vc, self.pos, None, decode=False)
-        self.pos.fill_(T - 1)
-        self.lens.fill_(T)
-        self.tok_buf.fill_(ids[-1])
-        if self.use_graphs and self.graph is None:
-            self._capture()
-        for _ in range(max_new):
-            if self.graph is not None:
-                self.graph.replay()
-            else:
-                self._step()
-        out = self.out[:max_new, 0].tolist()
-        if self.tok.eos in out:
-            out = out[:out.index(self.tok.eos)]
-        return out
-
-    def generate_text(self, prompt: str, min_new_tokens: int, max_new_tokens: int) -> str:
-        # rooms call generators from worker threads; the static decode buffers are single-user
-        with self._lock:
-            ids = self.generate_ids(self.tok.encode(prompt), min_new_tokens, max_new_tokens)
-        return self.tok.decode(ids)
-
-    # ---------------------------------------------------------------- batch decode (noise="philox")
     def _bucket(self, n: int) -> _Bucket:
         B = next(b for b in self.bucket_sizes if b >= n)
         if B not in self.buckets:
             self.buckets[B] = _Bucket(self, B)
         return self.buckets[B]
 
-    def _step_batch(self, bk: _Bucket) -> None:
+    # one decode step entirely on device buffers (captured as a graph on GPU)
+    def _step(self, bk: _Bucket) -> None:
         logits = self.model(bk.tok.view(bk.B, 1), bk.kc, bk.vc, bk.pos, bk.lens, decode=True)
-        # top-k + Gumbel-max per row, the noise drawn in the kernel from the row's seed and step
-        ops.lm_sample_seeded(logits, bk.seeds, self.eos_bias, self.tok.eos, self.temperature, self.top_k, bk.step,
-                             bk.out, bk.tok, bk.pos, bk.lens)
+        # top-k + Gumbel-max per row and the token / position / length / step update: one in-tree
+        # kernel on the GPU (lm_sample.hip), no ATen sampling ops.  The noise is this step's row of
+        # the table, or drawn in the kernel from the row's seed and step
+        sample, noise = (ops.lm_sample, bk.noise) if self.noise_mode == "table" else (ops.lm_sample_seeded, bk.seeds)
+        sample(logits, noise, self.eos_bias, self.tok.eos, self.temperature, self.top_k, bk.step, bk.out, bk.tok,
+               bk.pos, bk.lens)
 
-    def _capture_batch(self, bk: _Bucket) -> None:
+    def _capture(self, bk: _Bucket) -> None:
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         saved = [t.clone() for t in bk.state()]
         with torch.cuda.stream(s):
-            self._step_batch(bk)
+            self._step(bk)
         torch.cuda.current_stream().wait_stream(s)
         for t, v in zip(bk.state(), saved):
             t.copy_(v)
         g = torch.cuda.CUDAGraph()
         with TRACER.capturing(), torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._step_batch(bk)
+            self._step(bk)
         for t, v in zip(bk.state(), saved):
             t.copy_(v)
         bk.graph = g
+
+    @torch.no_grad()
+    def generate_ids(self, prompt_ids: Sequence[int], min_new: int, max_new: int) -> List[int]:
+        if self.noise_mode == "philox":
+            return self.generate_ids_batch([prompt_ids], min_new, max_new)[0]
+        t_host = time.perf_counter()
+        max_new = max(1, min(max_new, self.max_new_cap))
+        gen = torch.Generator(device="cpu").manual_seed(self.seed * 1000003 + self.calls)
+        u = torch.rand((max_new, 1, self.cfg.vocab), generator=gen).clamp_(1e-10, 1.0 - 1e-7)
+        self._bucket(1).noise[:max_new].copy_((-torch.log(-torch.log(u))).to(self.device))
+        return self._decode([prompt_ids], min_new, max_new, None, t_host)[0]
+
+    def generate_text(self, prompt: str, min_new_tokens: int, max_new_tokens: int) -> str:
+        # rooms call generators from worker threads; the static decode buffers are single-user
+        with self._lock:
+            ids = self.generate_ids(self.tok.encode(prompt), min_new_tokens, max_new_tokens)
+        return self.tok.decode(ids)
 
     @torch.no_grad()
     def generate_ids_batch(self, prompts: Sequence[Sequence[int]], min_new: int, max_new: int,
@@ -372,7 +321,13 @@ class LMTextGenerator:
             raise ValueError(f"{n} sequences exceed max_batch={self.max_batch}")
         if seeds is not None and len(seeds) != n:
             raise ValueError("one seed per sequence")
-        t_host = time.perf_counter()
+        return self._decode(prompts, min_new, max_new, seeds, time.perf_counter())
+
+    def _decode(self, prompts, min_new: int, max_new: int, seeds, t_host: float) -> List[List[int]]:
+        """The one decode loop: rows and their state set up on the host, one padded prefill, the
+        state uploaded, the bucket's step captured once and replayed ``max_new`` times.  ``t_host``:
+        when the call began; its host part (``host_ms``) ends before the first launch here."""
+        n = len(prompts)
         bk = self._bucket(n)
         B, dev = bk.B, self.device
         max_new = max(1, min(max_new, self.max_new_cap))
@@ -400,7 +355,8 @@ class LMTextGenerator:
         self.host_ms = (time.perf_counter() - t_host) * 1e3
         self.eos_bias.copy_(eb.to(dev))
         bk.step.zero_()
-        bk.seeds.copy_(bk.h_seeds, non_blocking=True)
+        if bk.noise is None:                          # the table sampler reads no seeds
+            bk.seeds.copy_(bk.h_seeds, non_blocking=True)
         if pre is not None:
             bk.pos.zero_()
             self.model(pre.to(dev), bk.kc, bk.vc, bk.pos, None, decode=False)
@@ -408,12 +364,12 @@ class LMTextGenerator:
         bk.lens.copy_(bk.h_lens, non_blocking=True)
         bk.tok.copy_(bk.h_tok, non_blocking=True)
         if self.use_graphs and bk.graph is None:
-            self._capture_batch(bk)
+            self._capture(bk)
         for _ in range(max_new):
             if bk.graph is not None:
                 bk.graph.replay()
             else:
-                self._step_batch(bk)
+                self._step(bk)
         out = bk.out[:max_new, :n].t().tolist()       # the one sync; also orders the pinned rows' reuse
         eos = self.tok.eos
         return [r[:r.index(eos)] if eos in r else r for r in out]

@@ -585,7 +585,7 @@ def lm_sample(logits: torch.Tensor, noise: torch.Tensor, eos_bias: torch.Tensor,
               k: int, step: torch.Tensor, out: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor,
               lens: torch.Tensor) -> None:
     """One decode step's sampling (top-k + Gumbel-max) and device-state update, batch 1:
-    ``ops.reference.lm_sample`` is the contract; on the GPU one in-tree kernel (lm.hip)."""
+    ``ops.reference.lm_sample`` is the contract; on the GPU one in-tree kernel (lm_sample.hip)."""
     if not _use_hip(logits):
         return ref.lm_sample(logits, noise, eos_bias, eos, temperature, k, step, out, tok, pos, lens)
     ext().lm_sample(logits.contiguous(), noise, eos_bias, int(eos), float(temperature), int(k), step, out, tok, pos,
@@ -599,7 +599,7 @@ def lm_sample_seeded(logits: torch.Tensor, seeds: torch.Tensor, eos_bias: torch.
     kernel from each row's seed and own step counter (no noise table): logits [B, V] bf16 / fp32
     (rows may be strided), seeds / step / tok [B] int64, pos / lens [B] int32, eos_bias [steps],
     out [steps, B].  ``ops.reference.lm_sample_seeded`` is the contract; on the GPU one in-tree
-    kernel (lm_sample_seeded.hip)."""
+    kernel (lm_sample.hip, the core of ``lm_sample``)."""
     if not _use_hip(logits):
         return ref.lm_sample_seeded(logits, seeds, eos_bias, eos, temperature, k, step, out, tok, pos, lens)
     if logits.dim() != 2 or logits.stride(1) != 1:

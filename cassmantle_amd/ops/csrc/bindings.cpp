@@ -826,56 +826,32 @@ void rope_kv(const at::Tensor& qkv, const at::Tensor& pos0, at::Tensor& q_out, a
   launch_rope_kv(a, cur_stream());
 }
 
-// one query token per sequence: q [B, H, d], caches [B, L, Hk, d], lens [B] -> out [B, H, d]
-void lm_sample(const at::Tensor& logits, const at::Tensor& noise, const at::Tensor& eos_bias, int64_t eos,
-               double temperature, int64_t k, at::Tensor& step, at::Tensor& out, at::Tensor& tok, at::Tensor& pos,
-               at::Tensor& lens) {
-  CHECK_DEV(logits); CHECK_CONTIG(logits); CHECK_CONTIG(noise); CHECK_CONTIG(out);
-  const int64_t V = logits.size(-1);
-  TORCH_CHECK(logits.numel() == V, "lm_sample: batch-1 logits [1, V]");
-  TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16, "lm_sample: f32 / bf16 logits");
-  TORCH_CHECK(noise.scalar_type() == at::kFloat && noise.numel() % V == 0, "lm_sample: noise [steps, 1, V] f32");
-  TORCH_CHECK(eos_bias.scalar_type() == at::kFloat && eos_bias.numel() == noise.numel() / V,
-              "lm_sample: eos_bias [steps] f32");
-  TORCH_CHECK(out.scalar_type() == at::kLong && out.numel() == eos_bias.numel(), "lm_sample: out [steps, 1] int64");
-  TORCH_CHECK(step.scalar_type() == at::kLong && tok.scalar_type() == at::kLong && step.numel() == 1 && tok.numel() == 1,
-              "lm_sample: step / token int64 scalars");
-  TORCH_CHECK(pos.scalar_type() == at::kInt && lens.scalar_type() == at::kInt, "lm_sample: pos / lens int32");
-  TORCH_CHECK(k >= 1 && temperature > 0, "lm_sample: k >= 1, temperature > 0");
-  launch_lm_sample(logits.data_ptr(), logits.scalar_type() == at::kFloat, (int)V, noise.data_ptr<float>(),
-                   eos_bias.data_ptr<float>(), (int)eos, (float)temperature, (int)k,
-                   reinterpret_cast<long long*>(step.data_ptr<int64_t>()), reinterpret_cast<long long*>(out.data_ptr<int64_t>()),
-                   reinterpret_cast<long long*>(tok.data_ptr<int64_t>()), pos.data_ptr<int>(), lens.data_ptr<int>(),
-                   cur_stream());
-}
-
-// batched sampler with in-kernel Gumbel noise: logits [B, V] (rows may be strided), per-row state
-void lm_sample_seeded(const at::Tensor& logits, const at::Tensor& seeds, const at::Tensor& eos_bias, int64_t eos,
-                      double temperature, int64_t k, at::Tensor& step, at::Tensor& out, at::Tensor& tok,
-                      at::Tensor& pos, at::Tensor& lens) {
-  CHECK_DEV(logits); CHECK_DEV(seeds); CHECK_DEV(eos_bias); CHECK_DEV(step); CHECK_DEV(out); CHECK_DEV(tok);
-  CHECK_DEV(pos); CHECK_DEV(lens);
-  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1),
-              "lm_sample_seeded: logits [B, V] with contiguous rows");
+// what the two sampler entry points share: logits [B, V] (rows may be strided), the per-row state
+// step / tok [B] int64, pos / lens [B] int32, eos_bias [steps], out [steps, B]; `fn` names the caller
+static LmSampleArgs lm_sample_args(const char* fn, const at::Tensor& logits, const at::Tensor& eos_bias, int64_t eos,
+                                   double temperature, int64_t k, at::Tensor& step, at::Tensor& out, at::Tensor& tok,
+                                   at::Tensor& pos, at::Tensor& lens) {
+  CHECK_DEV(logits); CHECK_DEV(eos_bias); CHECK_DEV(step); CHECK_DEV(out); CHECK_DEV(tok); CHECK_DEV(pos);
+  CHECK_DEV(lens);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= logits.size(1), fn,
+              ": logits [B, V] with contiguous rows");
   const int64_t B = logits.size(0), V = logits.size(1);
-  TORCH_CHECK(B >= 1 && B <= 8 && V >= 1 && V < (int64_t(1) << 31), "lm_sample_seeded: 1 <= B <= 8, 1 <= V < 2^31");
-  TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16,
-              "lm_sample_seeded: f32 / bf16 logits");
-  CHECK_CONTIG(seeds); CHECK_CONTIG(eos_bias); CHECK_CONTIG(step); CHECK_CONTIG(out); CHECK_CONTIG(tok);
-  CHECK_CONTIG(pos); CHECK_CONTIG(lens);
-  TORCH_CHECK(seeds.scalar_type() == at::kLong && seeds.numel() == B, "lm_sample_seeded: seeds [B] int64");
-  TORCH_CHECK(eos_bias.scalar_type() == at::kFloat && eos_bias.numel() >= 1, "lm_sample_seeded: eos_bias [steps] f32");
+  TORCH_CHECK(B >= 1 && B <= 8 && V >= 1 && V < (int64_t(1) << 31), fn, ": 1 <= B <= 8, 1 <= V < 2^31");
+  TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16, fn, ": f32 / bf16 logits");
+  CHECK_CONTIG(eos_bias); CHECK_CONTIG(step); CHECK_CONTIG(out); CHECK_CONTIG(tok); CHECK_CONTIG(pos);
+  CHECK_CONTIG(lens);
+  TORCH_CHECK(eos_bias.scalar_type() == at::kFloat && eos_bias.numel() >= 1, fn, ": eos_bias [steps] f32");
   const int64_t steps = eos_bias.numel();
-  TORCH_CHECK(steps < (int64_t(1) << 31), "lm_sample_seeded: too many steps");
-  TORCH_CHECK(out.scalar_type() == at::kLong && out.numel() == steps * B, "lm_sample_seeded: out [steps, B] int64");
+  TORCH_CHECK(steps < (int64_t(1) << 31), fn, ": too many steps");
+  TORCH_CHECK(out.scalar_type() == at::kLong && out.numel() == steps * B, fn, ": out [steps, B] int64");
   TORCH_CHECK(step.scalar_type() == at::kLong && tok.scalar_type() == at::kLong && step.numel() == B && tok.numel() == B,
-              "lm_sample_seeded: step / token [B] int64");
+              fn, ": step / token [B] int64");
   TORCH_CHECK(pos.scalar_type() == at::kInt && lens.scalar_type() == at::kInt && pos.numel() == B && lens.numel() == B,
-              "lm_sample_seeded: pos / lens [B] int32");
-  TORCH_CHECK(k >= 1 && temperature > 0, "lm_sample_seeded: k >= 1, temperature > 0");
-  LmSampleSeededArgs a;
+              fn, ": pos / lens [B] int32");
+  TORCH_CHECK(k >= 1 && temperature > 0, fn, ": k >= 1, temperature > 0");
+  LmSampleArgs a;
   a.logits = logits.data_ptr(); a.ld = logits.stride(0);
-  a.seeds = reinterpret_cast<const long long*>(seeds.data_ptr<int64_t>());
+  a.noise = nullptr; a.seeds = nullptr;
   a.eos_bias = eos_bias.data_ptr<float>();
   a.step = reinterpret_cast<long long*>(step.data_ptr<int64_t>());
   a.out = reinterpret_cast<long long*>(out.data_ptr<int64_t>());
@@ -884,7 +860,33 @@ void lm_sample_seeded(const at::Tensor& logits, const at::Tensor& seeds, const a
   a.B = (int)B; a.V = (int)V; a.k = (int)std::min<int64_t>(k, V);
   a.eos = (eos >= 0 && eos < V) ? (int)eos : -1;   // an eos outside the vocabulary biases nothing
   a.steps = (int)steps; a.temp = (float)temperature;
-  launch_lm_sample_seeded(a, logits.scalar_type() == at::kFloat, cur_stream());
+  return a;
+}
+
+// batch-1 sampler, the Gumbel noise read from row `step` of a [steps, 1, V] table
+void lm_sample(const at::Tensor& logits, const at::Tensor& noise, const at::Tensor& eos_bias, int64_t eos,
+               double temperature, int64_t k, at::Tensor& step, at::Tensor& out, at::Tensor& tok, at::Tensor& pos,
+               at::Tensor& lens) {
+  CHECK_DEV(noise); CHECK_CONTIG(logits); CHECK_CONTIG(noise);
+  const int64_t V = logits.size(-1);
+  TORCH_CHECK(logits.numel() == V, "lm_sample: batch-1 logits [1, V]");
+  LmSampleArgs a = lm_sample_args("lm_sample", logits.view({1, V}), eos_bias, eos, temperature, k, step, out, tok, pos,
+                                  lens);
+  TORCH_CHECK(noise.scalar_type() == at::kFloat && noise.numel() == (int64_t)a.steps * V,
+              "lm_sample: noise [steps, 1, V] f32");
+  a.noise = noise.data_ptr<float>();
+  launch_lm_sample(a, logits.scalar_type() == at::kFloat, cur_stream());
+}
+
+// batched sampler with in-kernel Gumbel noise, keyed by each row's seed and own step counter
+void lm_sample_seeded(const at::Tensor& logits, const at::Tensor& seeds, const at::Tensor& eos_bias, int64_t eos,
+                      double temperature, int64_t k, at::Tensor& step, at::Tensor& out, at::Tensor& tok,
+                      at::Tensor& pos, at::Tensor& lens) {
+  LmSampleArgs a = lm_sample_args("lm_sample_seeded", logits, eos_bias, eos, temperature, k, step, out, tok, pos, lens);
+  CHECK_DEV(seeds); CHECK_CONTIG(seeds);
+  TORCH_CHECK(seeds.scalar_type() == at::kLong && seeds.numel() == a.B, "lm_sample_seeded: seeds [B] int64");
+  a.seeds = reinterpret_cast<const long long*>(seeds.data_ptr<int64_t>());
+  launch_lm_sample(a, logits.scalar_type() == at::kFloat, cur_stream());
 }
 
 // the sampler's noise alone: out[b, j] = g(seeds[b], step, ids[j])
@@ -900,6 +902,7 @@ void lm_gumbel(const at::Tensor& seeds, int64_t step, const at::Tensor& ids, at:
                    out.data_ptr<float>(), cur_stream());
 }
 
+// one query token per sequence: q [B, H, d], caches [B, L, Hk, d], lens [B] -> out [B, H, d]
 void decode_attention(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
                       const at::Tensor& lens, at::Tensor& out, double scale) {
   CHECK_DEV(q); CHECK_BF16(q); CHECK_BF16(k_cache); CHECK_CONTIG(k_cache); CHECK_CONTIG(v_cache);

@@ -166,17 +166,15 @@ struct DecodeArgs {
   float scale;
 };
 int decode_splits(int B, int Hk, int L);
-// decode-step sampler (batch 1): top-k of logits / T (+ EOS bias of the step) + Gumbel-max with
-// the step's noise row, then token / position / length / step counter updated on the device
-void launch_lm_sample(const void* logits, int logits_f32, int V, const float* noise, const float* eos_bias, int eos,
-                      float temperature, int k, long long* step, long long* out, long long* tok, int* pos, int* lens,
-                      hipStream_t s);
 void launch_decode_attention(const DecodeArgs& a, int ns, hipStream_t s);
-// batched decode-step sampler, Gumbel noise drawn in the kernel (lm_sample_seeded.hip, the GUMBEL
-// CONTRACT of philox_gumbel.h): one workgroup per row, every row with its own seed and step counter
-struct LmSampleSeededArgs {
+// decode-step sampler (lm_sample.hip): top-k of logits / T (+ EOS bias of the row's step) + Gumbel-max,
+// then token / position / length / step counter updated on the device; one workgroup per row, every
+// row with its own step counter.  The noise is either row `step` of a table (batch 1, seeds null) or
+// drawn in the kernel from the row's seed (the GUMBEL CONTRACT of philox_gumbel.h, noise null)
+struct LmSampleArgs {
   const void* logits; long long ld;    // [B][V] bf16 / fp32, row stride in elements
-  const long long* seeds;              // [B] 64-bit sequence seeds
+  const float* noise;                  // [steps][1][V] table, or null
+  const long long* seeds;              // [B] 64-bit sequence seeds, or null
   const float* eos_bias;               // [steps]
   long long* step;                     // [B] per-row step counters
   long long* out;                      // [steps][B]
@@ -185,7 +183,7 @@ struct LmSampleSeededArgs {
   int B, V, k, eos, steps;
   float temp;
 };
-void launch_lm_sample_seeded(const LmSampleSeededArgs& a, int logits_f32, hipStream_t s);
+void launch_lm_sample(const LmSampleArgs& a, int logits_f32, hipStream_t s);
 // out[b][j] = g(seeds[b], step, ids[j]) fp32
 void launch_lm_gumbel(const long long* seeds, unsigned step, const long long* ids, int n, int B, float* out,
                       hipStream_t s);

@@ -1,6 +1,6 @@
 // Counter-based Gumbel noise for the LM decode sampler: Philox4x32-10 (philox_normal.h) and
 // g = -ln(-ln u).  Plain functions over words, compiled as they stand by lm_sample_seeded_kernel
-// and lm_gumbel_kernel (lm_sample_seeded.hip) and by a host program
+// and lm_gumbel_kernel (lm_sample.hip) and by a host program
 // (tests/native/philox_gumbel_host.cpp).  models/schedulers.py holds the numpy model
 // (philox_gumbel).
 //

@@ -273,19 +273,24 @@ def mean_pool_l2(hidden, lens):
     return s / s.norm(dim=-1, keepdim=True).clamp_min(1e-12)
 
 
+def _lm_topk(v, eos: int, bias, k: int):
+    """The samplers' top-k set: v [1, V] (logits / T, a fresh tensor: changed in place) with ``bias``
+    added at ``eos``, sorted descending and stable (ties keep the LOWER id), the first k: (values,
+    ids), each [1, k]."""
+    if 0 <= eos < v.shape[-1]:
+        v[:, eos] += bias
+    srt = torch.sort(v, dim=-1, descending=True, stable=True)
+    return srt.values[:, :k], srt.indices[:, :k]
+
+
 def lm_sample(logits, noise, eos_bias, eos: int, temperature: float, k: int, step, out, tok, pos, lens) -> None:
-    """Decode-step sampler (the contract of lm.hip's lm_sample_kernel), graph-capturable: v =
+    """Decode-step sampler (the contract of lm_sample.hip's lm_sample_kernel), graph-capturable: v =
     logits / T with the step's EOS bias added at ``eos``; the k largest v (stable: ties keep the
     LOWER id); the id maximising v + noise[step] among them (first in that order on ties); then
     out[step] = tok = id and pos, lens, step advance by one.  -0.0 and +0.0 are equal in that
     sort, so of two zeros the lower id ranks first whatever their signs; the kernel turns -0.0
     into +0.0 before it builds its keys to rank them the same way."""
-    lg = logits.float().reshape(1, -1) / temperature
-    V = lg.shape[-1]
-    if 0 <= eos < V:
-        lg[:, eos] += eos_bias.index_select(0, step)
-    srt = torch.sort(lg, dim=-1, descending=True, stable=True)
-    vals, ids = srt.values[:, :k], srt.indices[:, :k]
+    vals, ids = _lm_topk(logits.float().reshape(1, -1) / temperature, eos, eos_bias.index_select(0, step), k)
     g = noise.index_select(0, step)[0].gather(1, ids)
     choice = (vals + g).argmax(dim=-1, keepdim=True)
     nxt = ids.gather(1, choice)[:, 0]
@@ -314,14 +319,9 @@ def lm_sample_seeded(logits, seeds, eos_bias, eos: int, temperature: float, k: i
     depend on the other rows.  Reads the counters on the host: not graph-capturable."""
     from ..models.schedulers import philox_gumbel
     lg = logits.float() / temperature
-    B, V = lg.shape
     steps, sds = step.tolist(), seeds.tolist()
-    for b in range(B):
-        v = lg[b:b + 1].clone()
-        if 0 <= eos < V:
-            v[:, eos] += eos_bias[steps[b]]
-        srt = torch.sort(v, dim=-1, descending=True, stable=True)
-        vals, ids = srt.values[0, :k].cpu(), srt.indices[0, :k].cpu()
+    for b in range(lg.shape[0]):
+        vals, ids = (t[0].cpu() for t in _lm_topk(lg[b:b + 1], eos, eos_bias[steps[b]], k))
         g = philox_gumbel([sds[b]], steps[b], ids.numpy())[0]
         nxt = int(ids[int((vals.double().numpy() + g).argmax())])
         out[steps[b], b] = nxt

@@ -271,7 +271,7 @@ def test_lm_gpu_decode_and_graph(hip):
     graph = LMTextGenerator(cfg, device="cuda", seed=5, use_graphs=True)
     a = eager.generate_ids([256, 10, 20, 30], 24, 24)
     b = graph.generate_ids([256, 10, 20, 30], 24, 24)
-    assert graph.graph is not None
+    assert graph.buckets[1].graph is not None
     assert len(a) == len(b) == 24
     assert sum(x == y for x, y in zip(a, b)) >= 20   # bf16 near-ties may flip a late sample
     c = graph.generate_ids([256, 10, 20, 30], 24, 24)   # graph replays with fresh noise / state

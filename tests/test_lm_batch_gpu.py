@@ -1,5 +1,5 @@
-"""The batched, seeded LM sampler on the GPU (lm_sample_seeded.hip) and LMTextGenerator's batch
-decode on tiny-lm.
+"""The batched, seeded LM sampler on the GPU (lm_sample.hip, the core it shares with the table
+sampler) and LMTextGenerator's batch decode on tiny-lm.
 
 The sampler is held to the float64 model of its contract (ops.reference.lm_sample_seeded: the
 stable sort of the fp32 v, then schedulers.philox_gumbel in float64).  The kernel adds v + g in
@@ -165,6 +165,37 @@ def test_contiguous_and_strided_logits_agree_and_a_finished_row_is_left_alone():
     out, tok, pos, lens, step = st.read()
     assert step == [1, 4, 4] and tok[1] == -1 and pos == [1, 3, 7] and lens == [2, 4, 8]
     assert int((out != -1).sum()) == 2
+    # the table entry point too: at step 4 of 4 it changes nothing (State.read checks the guards)
+    st = State(1, 4, 4)
+    ops.lm_sample(ko.poisoned(lg[:1], device=DEV), torch.full((4, 1, 1025), math.nan, device=DEV),
+                  torch.zeros(4, device=DEV), 7, 0.8, 40, **st.args())
+    out, tok, pos, lens, step = st.read()
+    assert step == [4] and tok == [-1] and pos == [0] and lens == [1] and int((out != -1).sum()) == 0
+
+
+@pytest.mark.parametrize("dtype", [BF16, torch.float32], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("V", [300, 1025, 4097])
+def test_the_table_and_the_seeded_entry_points_are_one_sampler(V, dtype):
+    """ops.lm_sample on a table that is NaN except row ``step``, which holds the seeded kernel's
+    own noise (ops.lm_gumbel), and ops.lm_sample_seeded at B = 1 return the same token and state.
+    Over this grid (576 cases) the float64 model's smallest top-two gap is 2.6e-2, none is below
+    MARGIN, so both must also equal the model's winner outright."""
+    steps, T, eos = 96, 0.8, 7
+    lg = ko.rnd(1, V, scale=3.0, seed=V + 1, dtype=dtype)
+    lgp, eb, ids = ko.poisoned(lg, device=DEV), torch.zeros(steps, device=DEV), torch.arange(V, device=DEV)
+    for step in (0, 1, 95):
+        for seed in SEEDS:
+            table = torch.full((steps, 1, V), math.nan, device=DEV)
+            table[step, 0] = ops.lm_gumbel(seeds_dev([seed]), step, ids)[0]
+            for k in (1, 2, 40, min(V, 1000)):
+                a, b = State(1, steps, step), State(1, steps, step)
+                ops.lm_sample(lgp, table, eb, eos, T, k, **a.args())
+                ops.lm_sample_seeded(lgp, seeds_dev([seed]), eb, eos, T, k, **b.args())
+                ra, rb = a.read(), b.read()
+                assert torch.equal(ra[0], rb[0]) and ra[1:] == rb[1:], (V, dtype, k, step, seed)
+                assert ra[1:] == ([int(ra[0][step, 0])], [1], [2], [step + 1]) and int((ra[0] != -1).sum()) == 1
+                win, _, gap = model_choice(lg[0], T, k, eos, 0.0, seed, step)
+                assert gap >= MARGIN and ra[1] == [win], (V, dtype, k, step, seed, ra[1], win, gap)
 
 
 # ------------------------------------------------------------------------------ rank probes
