@@ -1,6 +1,6 @@
 """Instruments for localised kernel errors, shared by test_kernel_oracle.py (CPU: the instruments
-themselves, proven on planted bugs) and test_kernel_edges_gpu.py, test_kernel_edges_decode_gpu.py
-and test_kernel_edges_scorer_gpu.py (the HIP kernels).
+themselves, proven on planted bugs) and test_kernel_edges_gpu.py, test_kernel_edges_conv_gpu.py,
+test_kernel_edges_decode_gpu.py and test_kernel_edges_scorer_gpu.py (the HIP kernels).
 
 A whole-tensor ``|out - ref| / |ref|`` under 1e-2 passes a kernel that drops the bias of one row,
 leaves one padding key unmasked or normalises one row group with another's statistics.  Three
@@ -24,13 +24,13 @@ never hand a kernel a pointer whose tile-sized neighbourhood is unallocated.
 The ideal kernel (fp64 math, rounded only where the kernels' own headers say they round: the bf16
 output, the bf16 scaled Q and P of attention, the bf16 folded W*gamma of the LayerNorm fold, the
 bf16 normalised A rows of the GroupNorm fold, e4m3 Q/K/V/P of the fp8 attention) must stay under
-HALF the bound in every block of every case of the three GPU files; test_kernel_oracle.py
+HALF the bound in every block of every case of the four GPU files; test_kernel_oracle.py
 asserts that.  Its worst block, measured on the CPU over those cases (the table
 test_kernel_oracle.py::test_floor_table prints with ``-s``):
 
     family                block                      bound    ideal kernel's worst block
     gemm / linear_cat     16 rows x 16 columns       1e-2     2.81e-3
-    conv2d / conv2d_up2   16 pixels x 16 channels    1e-2     2.96e-3
+    conv2d / conv2d_up2   16 pixels x 16 channels    1e-2     2.96e-3   (the tile-by-tile cases: 2.13e-3)
     LayerNorm fold        16 rows x 16 columns       1.5e-2   3.98e-3
     GroupNorm fold        16 rows x 16 columns       1e-2     2.73e-3
     attention (bf16)      16 queries x d             2e-2     3.36e-3
@@ -58,7 +58,8 @@ Two things the kernels' own rules set.  Causal attention has no key that every q
 ignore (key q + 1 is masked for query q and valid for the queries after it), so the causal
 future key carries a large finite V (FUTURE_V) instead of 3e38, which would overflow the rows
 that may see it.  And the GEMM planner runs a forced tile only at shapes its family takes:
-:func:`gemm_cases` and the A-in-registers cases say where that moves a K or an N.
+:func:`gemm_cases`, :func:`conv_tile_cases` and the A-in-registers cases say where that moves a
+K or an N.
 """
 from __future__ import annotations
 
@@ -295,16 +296,161 @@ UP2_CASE = (2, 3, 5, 64, 72)
 UP2_SPLIT_CIN = 128          # a forced split-K plan needs eight k-tiles (K = 4 Cin): four per slice
 
 
-def conv_inputs(B, H, W, Cin, Cout, stride=1, up=False):
-    """x, w, bias, chan_bias, residual"""
-    s = 2000 + 31 * H + 5 * Cin + Cout + stride
+def conv_inputs(B, H, W, Cin, Cout, stride=1, up=False, ksize=3):
+    """x, w, bias, chan_bias, residual (``ksize`` 3: padding 1; 1: padding 0)"""
+    s = 2000 + 31 * H + 5 * Cin + Cout + stride + (0 if ksize == 3 else 977 * ksize)
     Ho, Wo = ((2 * H, 2 * W) if up else ((H - 1) // stride + 1, (W - 1) // stride + 1))
-    return (rnd(B, H, W, Cin, seed=s), rnd(Cout, 3, 3, Cin, scale=(9 * Cin) ** -0.5, seed=s + 1),
+    return (rnd(B, H, W, Cin, seed=s), rnd(Cout, ksize, ksize, Cin, scale=(ksize * ksize * Cin) ** -0.5, seed=s + 1),
             rnd(Cout, scale=0.1, seed=s + 2), rnd(B, Cout, scale=0.1, seed=s + 3), rnd(B, Ho, Wo, Cout, seed=s + 4))
 
 
-def conv64(x, w, b, cb, res, stride=1, up=False):
-    return ref.conv2d(x, w, b, stride, 1, res, up, cb, dtype=F64)
+def conv64(x, w, b, cb, res, stride=1, up=False, padding=1):
+    return ref.conv2d(x, w, b, stride, padding, res, up, cb, dtype=F64)
+
+
+# ---- the implicit-GEMM conv tile by tile (test_kernel_edges_conv_gpu.py)
+BK = 64                      # k-tile of every MFMA GEMM / conv kernel
+# (B, H, W, stride) of the input: the smallest that give a BM = 256 tile one full M tile and a
+# partial one, an image boundary inside a tile (135 / 150 output pixels per image) and a W that is
+# no multiple of 16.  s2: Ho x Wo = 10 x 15, the bottom edge padded (odd H), the right one not
+# (even W).  up: the low-res input of an 18 x 30 output.
+CONV_GEOM = {"s1": (2, 9, 15, 1), "s2": (2, 19, 30, 2), "up": (2, 9, 15, 1)}
+CONV_KINDS = ("s1", "s2", "up2")      # what a tuning-table entry can be: stride 1, stride 2, parity classes
+
+
+class ConvCase(NamedTuple):
+    group: str        # "plain" (ops.conv2d, 3x3) | "up2" (the parity classes) | "modes" (static tiles only)
+    cfg: int          # forced tile
+    split: int        # forced split-K
+    geom: str         # key of CONV_GEOM
+    Cin: int
+    Cout: int
+    stats: bool       # epilogue statistics (a split case: splitk_reduce_stats_kernel, else splitk_reduce_kernel)
+    op: str = "conv"  # "conv" | "up2" (conv2d_up2) | "fused_up" (conv2d(upsample=True)) | "1x1" (pad 0)
+
+    @property
+    def kind(self):
+        return "up2" if self.op == "up2" else self.geom
+
+    @property
+    def ksize(self):
+        return 1 if self.op == "1x1" else 3
+
+    @property
+    def K(self):
+        """the GEMM's K: taps x Cin (four taps per parity class)"""
+        return (4 if self.op == "up2" else self.ksize ** 2) * self.Cin
+
+    @property
+    def nk(self):
+        return -(-self.K // BK)
+
+    @property
+    def id(self):
+        return f"cfg{self.cfg}-s{self.split}-{self.op}-{self.geom}-{self.Cin}to{self.Cout}-{'stats' if self.stats else 'nostats'}"
+
+
+def split_slices(nk, split) -> list:
+    """k-tiles of every split-K slice as the kernels cut them: ``per = ceil(nk / split)`` each,
+    the last ones shorter or empty"""
+    per = -(-nk // split)
+    return [max(0, min(nk, (s + 1) * per) - s * per) for s in range(split)]
+
+
+def conv_tile_cases(menu) -> list:
+    """every live non-areg row of the tile menu on the conv A loader.  Cout = BN + 8 (one full, one
+    partial N tile; the N <= 16 tile: 16).  Per tile, Cin % 64 == 0: stride 1 and 2 at nk = 9; a
+    split in four of nk = 18 (slices of 5, 5, 5, 3: the last shorter than the 4- and 5-stage
+    rings, each starting in the middle of the taps); a split in seven of nk = 36 (six slices of
+    six, the seventh empty: its slab must be zeros); conv2d_up2 at nk = 4 and nk = 20 split in
+    three (7, 7, 6).  Split cases run with and without statistics: the two reduce kernels.  All
+    satisfy the planner's rules for a forced plan (family_runs: Cin % 64, N > 16, N % 8, ldcb % 4;
+    nk / split >= 4), so none tests its fallback.  The static tiles have the other A modes as
+    well: Cin = 32 / 24 (gemm_c1: tap boundaries inside a k-tile), the fused 2x upsample at
+    Cin = 64 (gemm_c3) / 32 (gemm_c1), a 1x1 pad-0 conv, and N % 8 != 0 through the plain reduce."""
+    cases = []
+    for cid, fam, BM, BN, *_ in menu:
+        if fam == "areg":
+            continue
+        N = 16 if BN <= 16 else BN + 8
+        cases += [ConvCase("plain", cid, 1, g, 64, N, True) for g in ("s1", "s2")]
+        cases += [ConvCase("plain", cid, s, "s1", cin, N, st) for s, cin in ((4, 128), (7, 256)) for st in (True, False)]
+        cases.append(ConvCase("up2", cid, 1, "up", 64, N, True, "up2"))
+        cases += [ConvCase("up2", cid, 3, "up", 320, N, st, "up2") for st in (True, False)]
+        if fam == "static":
+            cases += [ConvCase("modes", cid, 1, g, cin, N, True) for cin in (32, 24) for g in ("s1", "s2")]
+            cases += [ConvCase("modes", cid, 1, "up", cin, N, True, "fused_up") for cin in (64, 32)]
+            cases.append(ConvCase("modes", cid, 1, "s1", 64, N, True, "1x1"))
+            if cid == 3:
+                cases.append(ConvCase("modes", cid, 4, "s1", 128, BN + 4, False))
+    return cases
+
+
+_CONV_REF = {}
+
+
+def conv_case_data(c: ConvCase):
+    """(x, w, bias, chan_bias, residual), fp64 reference [B, Ho, Wo, Cout]; computed once per
+    geometry and channel counts and shared by every tile (do not modify)"""
+    B, H, W, stride = CONV_GEOM[c.geom]
+    up = c.op in ("up2", "fused_up")
+    key = (c.geom, c.Cin, c.Cout, up, c.ksize)
+    if key not in _CONV_REF:
+        args = conv_inputs(B, H, W, c.Cin, c.Cout, stride, up, c.ksize)
+        _CONV_REF[key] = (args, conv64(*args, stride=stride, up=up, padding=c.ksize // 2))
+    return _CONV_REF[key]
+
+
+def chan_bias_slice(cb: torch.Tensor, device=None) -> torch.Tensor:
+    """``cb`` [B, N] as a column slice of a wider NaN buffer whose row stride is a multiple of 8
+    and greater than N (ldcb != N: the batched time-embedding projection hands every ResNet its
+    columns of one wide output)"""
+    B, N = cb.shape
+    ld = (N + 7) // 8 * 8 + 16
+    buf = torch.full((B + 2, ld), math.nan, dtype=cb.dtype, device=cb.device if device is None else device)
+    view = buf[1:B + 1, 8:8 + N]
+    view.copy_(cb)
+    assert view.stride(0) > N and view.stride(0) % 8 == 0 and view.stride(1) == 1
+    return view
+
+
+def conv_im2col(x, ksize=3, stride=1, wrap_left=False, one_image=False) -> torch.Tensor:
+    """A [B * Ho * Wo, ksize^2 * Cin] of the implicit GEMM in fp64 (k = tap * Cin + channel,
+    padding ksize // 2).  The planted bugs of a linear tap offset without its mask:
+    ``wrap_left`` reads the left padding tap one pixel below the row's first, the previous row's
+    last pixel; ``one_image`` bounds the rows by the whole batch, so a tap above an image's first
+    row (below its last) reads the neighbouring image."""
+    B, H, W, Cin = x.shape
+    pad = ksize // 2
+    Ho, Wo = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
+    xf = torch.cat([x.to(F64).reshape(B * H * W, Cin), torch.zeros(1, Cin, dtype=F64)])      # last row: the zero page
+    b, oy, ox = torch.meshgrid(torch.arange(B), torch.arange(Ho), torch.arange(Wo), indexing="ij")
+    cols = []
+    for ky in range(ksize):
+        for kx in range(ksize):
+            iy, ix = oy * stride - pad + ky, ox * stride - pad + kx
+            flat = (b * H + iy) * W + ix
+            ok_y = ((b * H + iy >= 0) & (b * H + iy < B * H)) if one_image else ((iy >= 0) & (iy < H))
+            ok_x = (ix >= 0) & (ix < W)
+            if wrap_left:
+                ok_x = ok_x | ((ix == -1) & (flat >= 0))
+            cols.append(xf[torch.where(ok_y & ok_x, flat, torch.full_like(flat, B * H * W)).reshape(-1)])
+    return torch.cat(cols, dim=1)
+
+
+def conv_model(x, w, b, cb, res, stride=1, split=1, drop_slice=None, **bugs) -> torch.Tensor:
+    """the implicit GEMM in fp64, k-tile slices summed as the split-K reduce does, epilogue, bf16
+    store; [B, Ho, Wo, Cout].  ``drop_slice``: the planted reduce that leaves that slice out."""
+    Cout, ksize = w.shape[0], w.shape[1]
+    A = conv_im2col(x, ksize, stride, **bugs)
+    Wm = w.to(F64).reshape(Cout, -1)
+    y, kt = torch.zeros(A.shape[0], Cout, dtype=F64), 0
+    for s, n in enumerate(split_slices(-(-A.shape[1] // BK), split)):
+        if s != drop_slice:
+            y += A[:, kt * BK:(kt + n) * BK] @ Wm[:, kt * BK:(kt + n) * BK].t()
+        kt += n
+    y = y.view(res.shape) + b.to(F64) + cb.to(F64)[:, None, None, :] + res.to(F64)
+    return bf16_round(y)
 
 
 # ------------------------------------------------------------------------------ attention

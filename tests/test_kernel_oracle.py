@@ -1,7 +1,7 @@
 """The instruments of kernel_oracle.py, proven on the CPU with ``ops.reference`` as the kernel:
 the ideal kernel (fp64 math, one rounding where the HIP kernels round) stays under half the bound
-in every block of every case test_kernel_edges_gpu.py, test_kernel_edges_decode_gpu.py and
-test_kernel_edges_scorer_gpu.py run, and each planted bug -- those of the first file all get past
+in every block of every case test_kernel_edges_gpu.py, test_kernel_edges_conv_gpu.py,
+test_kernel_edges_decode_gpu.py and test_kernel_edges_scorer_gpu.py run, and each planted bug -- those of the first file all get past
 the whole-tensor error of tests/test_kernels_gpu.py -- fails its check.  The sampler, the top-k
 and mean_pool_l2 have models of the kernels' own selection rules here; their planted bugs are the
 ones those kernels had or could have (a tie cut one rank too wide, -0.0 keyed below +0.0, a
@@ -18,6 +18,13 @@ from kernel_oracle import BF16, BOUND, F64, bf16_round, block_rel_err
 from test_gemm_menu import header_rows
 
 FLOOR = {}      # table row -> (family, the ideal kernel's worst block over the cases run so far)
+CONV_TILE_CASES = ko.conv_tile_cases(header_rows())
+
+
+def _conv_case(**kw):
+    """a case of the table by its fields (the first that matches; tile 3 unless ``cfg`` is given)"""
+    kw.setdefault("cfg", 3)
+    return next(c for c in CONV_TILE_CASES if all(getattr(c, k) == v for k, v in kw.items()))
 
 
 def floor(family, err, what, row=None):
@@ -67,6 +74,24 @@ def test_ideal_conv():
     for cin in (Cin, ko.UP2_SPLIT_CIN):
         y64 = ko.conv64(*ko.conv_inputs(B, H, W, cin, Cout, up=True), up=True).flatten(0, 2)
         floor("conv", block_rel_err(bf16_round(y64), y64), ("up2", cin))
+    seen = set()
+    for c in CONV_TILE_CASES:                                  # the tiles share their data: once per reference
+        (x, w, b, cb, res), y64 = ko.conv_case_data(c)
+        if id(y64) not in seen:
+            seen.add(id(y64))
+            floor("conv", block_rel_err(bf16_round(y64).flatten(0, 2), y64.flatten(0, 2)), c.id, "conv, tile by tile")
+
+
+def test_conv_model_is_the_reference():
+    """the im2col model the planted conv bugs are cut from, sliced as split-K cuts it, is the
+    reference itself: within the bf16 store of it at every stride, kernel size and split"""
+    for c in (_conv_case(split=1, geom="s1"), _conv_case(split=1, geom="s2"), _conv_case(split=4, Cin=128),
+              _conv_case(split=7, Cin=256), _conv_case(group="modes", split=1, Cin=24, geom="s2"),
+              _conv_case(group="modes", split=1, op="1x1")):
+        args, y64 = ko.conv_case_data(c)
+        y = ko.conv_model(*args, stride=ko.CONV_GEOM[c.geom][3], split=c.split)
+        assert block_rel_err(y.flatten(0, 2), y64.flatten(0, 2)) < 0.5 * BOUND["conv"], c.id
+        assert (y != bf16_round(y64)).float().mean().item() < 1e-3, c.id       # (a summation order apart)
 
 
 @pytest.mark.parametrize("d", [32, 40, 64, 80, 160, 256, 512])
@@ -219,6 +244,107 @@ def test_nan_read_past_the_k_columns_of_a_strided_x_fails():
     assert math.isnan(flat[0].item()) and math.isnan(flat[-1].item())
     q = ko.poisoned(ko.rnd(3, 5, 2, 16), strided=True, row_dims=2)
     assert q.stride(1) == 2 * 16 + 16 and q.stride(2) == 16 and all(s % 8 == 0 for s in q.stride()[:3])
+
+
+# ------------------------------------------------------------------------------ planted conv bugs
+def _conv_bug(c, **kw):
+    """(block error of the planted bug, of the unharmed model) on case ``c``"""
+    args, y64 = ko.conv_case_data(c)
+    stride, y64 = ko.CONV_GEOM[c.geom][3], y64.flatten(0, 2)
+    good = block_rel_err(ko.conv_model(*args, stride=stride, split=c.split).flatten(0, 2), y64)
+    return block_rel_err(ko.conv_model(*args, stride=stride, split=c.split, **kw).flatten(0, 2), y64), good
+
+
+@pytest.mark.parametrize("geom", ["s1", "s2"])
+def test_conv_left_padding_tap_from_the_previous_row_fails(geom):
+    """the linear tap offset of the buffer modes without the per-lane tap mask: ix = -1 is the
+    previous row's last pixel"""
+    bad, good = _conv_bug(_conv_case(split=1, geom=geom, Cin=64), wrap_left=True)
+    assert bad > 2 * BOUND["conv"] and good < 0.5 * BOUND["conv"], (bad, good)
+
+
+@pytest.mark.parametrize("geom", ["s1", "s2"])
+def test_conv_two_images_as_one_tall_image_fails(geom):
+    """rows bounded by the batch, not the image: only the pixel rows next to the image boundary
+    differ (2 of 18 at stride 1, 1 of 20 at stride 2: the second image's top; the first one's
+    bottom row 18 is real padding of an odd H)"""
+    bad, good = _conv_bug(_conv_case(split=1, geom=geom, Cin=64), one_image=True)
+    assert bad > 2 * BOUND["conv"] and good < 0.5 * BOUND["conv"], (bad, good)
+
+
+@pytest.mark.parametrize("split,Cin", [(4, 128), (7, 256)])
+def test_split_k_sum_without_the_last_non_empty_slice_fails(split, Cin):
+    c = _conv_case(split=split, Cin=Cin)
+    last = max(s for s, n in enumerate(ko.split_slices(c.nk, c.split)) if n > 0)
+    bad, good = _conv_bug(c, drop_slice=last)
+    assert bad > 2 * BOUND["conv"] and good < 0.5 * BOUND["conv"], (bad, good)
+    if split == 7:                                             # the empty slice adds nothing
+        args, _ = ko.conv_case_data(c)
+        assert torch.equal(ko.conv_model(*args, split=7, drop_slice=6), ko.conv_model(*args, split=7))
+
+
+# ------------------------------------------------------------------------------ the conv case table
+def test_conv_case_table_structure():
+    """every live non-areg tile has a stride-1, a stride-2, a short-slice, an empty-slice and
+    an up2 case (plain and split), the split cases with either reduce kernel; the slices are
+    what ceil(nk / split) gives; the shapes are what the tiles need"""
+    assert ko.split_slices(18, 4) == [5, 5, 5, 3] and ko.split_slices(36, 7) == [6] * 6 + [0]
+    assert ko.split_slices(20, 3) == [7, 7, 6] and ko.split_slices(9, 1) == [9]
+    menu = [r for r in header_rows() if r[1] != "areg"]
+    assert {c.cfg for c in CONV_TILE_CASES} == {r[0] for r in menu}
+    assert len({c.id for c in CONV_TILE_CASES}) == len(CONV_TILE_CASES)
+    deepest = max(r[5] for r in menu)
+    for cid, fam, BM, BN, _, stages, *_ in menu:
+        mine = [c for c in CONV_TILE_CASES if c.cfg == cid]
+        have = lambda **kw: [c for c in mine if all(getattr(c, k) == v for k, v in kw.items())]   # noqa: E731
+        assert have(op="conv", geom="s1", split=1, Cin=64) and have(op="conv", geom="s2", split=1, Cin=64)
+        for split, nk, slices in ((4, 18, [5, 5, 5, 3]), (7, 36, [6] * 6 + [0])):
+            cs = have(op="conv", geom="s1", split=split, nk=nk)
+            assert {c.stats for c in cs if c.Cout % 8 == 0} == {True, False}, (cid, split)
+            assert ko.split_slices(nk, split) == slices and nk // split >= 4       # the planner's nk / split >= 4
+        assert min(ko.split_slices(18, 4)) < min(4, deepest) and ko.split_slices(36, 7)[-1] == 0
+        assert have(op="up2", split=1, nk=4) and {c.stats for c in have(op="up2", split=3, nk=20)} == {True, False}
+        for c in mine:
+            B, H, W, stride = ko.CONV_GEOM[c.geom]
+            up = 2 if c.op in ("up2", "fused_up") else 1
+            hw = ((H - 1) // stride + 1) * ((W - 1) // stride + 1) * (1 if c.op == "up2" else up * up)   # GEMM rows per image
+            M = B * hw
+            assert M > BM and M % BM != 0, (c.id, M)                             # a full M tile and a partial one
+            assert B == 2 and hw % BM != 0, c.id                                 # the image boundary inside a tile
+            assert W % 16 != 0 and (c.Cout == BN + 8 or (BN == 16 and c.Cout == 16) or c.Cout == BN + 4), c.id
+            assert (BN <= 16) == (c.Cout <= 16) and c.Cout % 4 == 0              # the BN <= 16 rule, can_split
+            assert c.split == 1 or c.nk // c.split >= 4, c.id
+            assert not c.stats or c.Cout % 8 == 0, c.id
+            if fam != "static":                                                    # family_runs
+                assert c.Cin % 64 == 0 and c.op in ("conv", "up2") and c.Cout > 16 and c.Cout % 8 == 0, c.id
+        if fam == "static":
+            assert {(c.Cin, c.geom) for c in have(group="modes", op="conv", split=1)} == {(ci, g) for ci in (32, 24) for g in ("s1", "s2")}
+            assert {c.Cin for c in have(op="fused_up")} == {64, 32} and have(op="1x1")
+    assert [c for c in CONV_TILE_CASES if c.Cout % 8 != 0 and c.split > 1 and not c.stats], "N % 8 != 0 through the plain reduce"
+
+
+def test_conv_cases_cover_the_tuning_table():
+    """every conv / conv2d_up2 entry of the committed tuning table: its (tile, kind) is in the
+    case table, and a tile the table splits has a split case of that kind's family (plain / up2)"""
+    import json
+    import os
+    import re
+    path = os.path.join(os.path.dirname(os.path.abspath(ops.__file__)), "gemm_tuning.json")
+    key = re.compile(r"^m\d+ n\d+ k\d+ w\d+ b\d+ c(\d+):\d+:\d+:\d+:(\d+):\d+:\d+:\d+ p(\d+) ")      # gemm_key (gemm.hip)
+    have = {(c.cfg, c.kind) for c in CONV_TILE_CASES}
+    have_split = {(c.cfg, c.op == "up2") for c in CONV_TILE_CASES if c.split > 1}
+    n = 0
+    for e in json.load(open(path))["entries"]:
+        m = key.match(e["key"])
+        assert m, e["key"]
+        conv, stride, parity = (int(v) for v in m.groups())
+        if not conv:
+            continue
+        n += 1
+        kind = "up2" if parity else {1: "s1", 2: "s2"}[stride]
+        assert kind in ko.CONV_KINDS and (int(e["cfg"]), kind) in have, e
+        assert int(e["split"]) == 1 or (int(e["cfg"]), bool(parity)) in have_split, e
+    assert n > 0
 
 
 def test_block_rel_err_blocks():
