@@ -201,6 +201,9 @@ class ModelConfig:
     lm_noise: str = "table"
     lm_batch_max: int = 1                 # rooms' prompts decoded as one LM batch (1..8; > 1 needs lm_noise=philox)
     lm_batch_window_ms: float = 50.0      # how long the batch leader waits for the other rooms' requests
+    # the LM's projection weights: bf16 | fp8 (weight-only e4m3 rows with one scale per row, quantised
+    # after the checkpoint is loaded; half the bytes per token, ops/csrc/lm_fp8.hip)
+    lm_weight_dtype: str = "bf16"
     # --- remote generation (reference parity: HF inference endpoints, src/backend.py:24-25) ---
     remote_prompt_url: Optional[str] = None
     remote_image_url: Optional[str] = None

@@ -21,6 +21,11 @@ already hosts the diffusion pipeline (7B bf16 = 14.5 GB of the 288 GB HBM):
   position for all of them (``generate_ids_batch``, buckets of 1, 2, 4, 8 rows with a captured
   graph each).
 
+* ``weight_dtype="fp8"`` (``CausalLM.quantize_fp8_``): every projection becomes e4m3 codes with one
+  scale per row (the RMSNorm gains folded in, ``embed`` stays bf16) and decode streams them through
+  ``ops.linear_fp8`` (ops/csrc/lm_fp8.hip): half the bytes per token.  Prefill over more than 8
+  rows dequantises one projection at a time into one scratch buffer and runs the bf16 GEMM.
+
 Weights are random-init by default (no checkpoints on the box); ``models/weights.py``
 ``load_causal_lm`` maps a HF-layout safetensors checkpoint in.  Without a real tokenizer a
 byte-level tokenizer is used, so random weights emit unusable text and
@@ -107,13 +112,25 @@ class LMBlock(nn.Module):
         self.o = _randn((c.dim, c.heads * hd), 1.0 / math.sqrt(c.dim * 2 * c.layers), gen, device, dtype)
         self.gate_up = _randn((2 * c.ffn, c.dim), 1.0 / math.sqrt(c.dim), gen, device, dtype)  # [up; gate]
         self.down = _randn((c.dim, c.ffn), 1.0 / math.sqrt(c.ffn * 2 * c.layers), gen, device, dtype)
+        self.quantized = False
 
-    def forward(self, x, kc, vc, pos0, lens, decode: bool):
-        """x [B, T, dim]; kc/vc [B, L, Hk, hd] cache of this layer."""
+    def quantize_fp8_(self) -> None:
+        """bf16 projections -> (codes, scale) buffers ``<name>_q`` / ``<name>_s`` (ops.quantize_rows_fp8);
+        the RMSNorm gains go into qkv / gate_up and become ones; the bf16 projections are freed."""
+        for name, gain in (("qkv", self.attn_norm), ("o", None), ("gate_up", self.mlp_norm), ("down", None)):
+            _quantize_param(self, name, gain)
+        self.quantized = True
+
+    def forward(self, x, kc, vc, pos0, lens, decode: bool, scratch=None):
+        """x [B, T, dim]; kc/vc [B, L, Hk, hd] cache of this layer.  ``scratch``: the quantised
+        model's dequantisation buffer (prefill over more than 8 rows)."""
         c = self.c
         B, T, _ = x.shape
         hd = c.head_dim
-        qkv = ops.rms_linear(x, self.attn_norm, c.eps, self.qkv)
+        if self.quantized:
+            qkv = ops.linear_fp8(x, self.qkv_q, self.qkv_s, rms_eps=c.eps, scratch=scratch)
+        else:
+            qkv = ops.rms_linear(x, self.attn_norm, c.eps, self.qkv)
         q = torch.empty((B, T, c.heads, hd), device=x.device, dtype=x.dtype)
         ops.rope_kv(qkv, pos0, q, kc, vc, c.heads, c.kv_heads, c.rope_theta)
         if decode:
@@ -121,9 +138,33 @@ class LMBlock(nn.Module):
         else:
             # prefill from position 0: causal flash attention over the freshly written cache rows
             o = ops.attention(q, kc[:, :T], vc[:, :T], causal=True)
+        if self.quantized:
+            x = ops.linear_fp8(o.reshape(B, T, c.heads * hd), self.o_q, self.o_s, residual=x, scratch=scratch)
+            h = ops.linear_fp8(x, self.gate_up_q, self.gate_up_s, act="swiglu", rms_eps=c.eps, scratch=scratch)
+            return ops.linear_fp8(h, self.down_q, self.down_s, residual=x, scratch=scratch)
         x = ops.linear(o.reshape(B, T, c.heads * hd), self.o, residual=x)
         h = ops.rms_linear(x, self.mlp_norm, c.eps, self.gate_up, act="swiglu")
         return ops.linear(h, self.down, residual=x)
+
+
+def _quantize_param(mod: nn.Module, name: str, gain: Optional[nn.Parameter]) -> None:
+    """``mod.<name>`` [Nw, K] bf16 (times ``gain`` [K], which becomes ones) -> buffers ``<name>_q``
+    uint8 and ``<name>_s`` fp32; the parameter is deleted."""
+    w = getattr(mod, name)
+    q, s = ops.quantize_rows_fp8(w.data, None if gain is None else gain.data)
+    delattr(mod, name)
+    mod.register_buffer(name + "_q", q)
+    mod.register_buffer(name + "_s", s)
+    if gain is not None:
+        gain.data.fill_(1.0)
+
+
+def _weight_f32(mod: nn.Module, name: str) -> torch.Tensor:
+    """fp32 projection ``name`` of a block or model: the bf16 parameter, or e4m3(q) * scale"""
+    if hasattr(mod, name + "_q"):
+        from ..ops import reference as R
+        return R.dequantize_rows_fp8(getattr(mod, name + "_q"), getattr(mod, name + "_s"), dtype=torch.float32)
+    return getattr(mod, name).float()
 
 
 class CausalLM(nn.Module):
@@ -136,6 +177,38 @@ class CausalLM(nn.Module):
         self.blocks = nn.ModuleList([LMBlock(c, gen, device, dtype) for _ in range(c.layers)])
         self.norm = nn.Parameter(torch.ones(c.dim, device=device, dtype=dtype), requires_grad=False)
         self.lm_head = _randn((c.vocab, c.dim), 1.0 / math.sqrt(c.dim), gen, device, dtype)
+        self.quantized = False
+        self._scratch: Optional[torch.Tensor] = None
+
+    @torch.no_grad()
+    def quantize_fp8_(self) -> "CausalLM":
+        """Weight-only fp8, in place (weight contract: ops/csrc/lm_fp8.hip): qkv, gate_up and lm_head
+        with their RMSNorm gain folded in (the gains become ones), o and down as they are; the bf16
+        projections are freed one by one, ``embed`` stays bf16.  Load a checkpoint first, then
+        quantise: a second call raises."""
+        if self.quantized:
+            raise RuntimeError("CausalLM.quantize_fp8_: the model is quantised already")
+        for blk in self.blocks:
+            blk.quantize_fp8_()
+        _quantize_param(self, "lm_head", self.norm)
+        self.quantized = True
+        return self
+
+    def weight_bytes(self) -> int:
+        """bytes one decode step streams: every projection (codes and scales, or bf16), not ``embed``"""
+        skip = {id(self.embed)}
+        ts = [p for p in self.parameters() if id(p) not in skip] + list(self.buffers())
+        return sum(t.numel() * t.element_size() for t in ts)
+
+    def _prefill_scratch(self, rows: int) -> Optional[torch.Tensor]:
+        """the one dequantisation buffer of a quantised model, sized for its largest projection (235 MB
+        at Mistral's gate_up) and made when a prefill over more than 8 rows first needs it"""
+        if not self.quantized or rows <= ops.FP8_GEMV_ROWS:
+            return None
+        if self._scratch is None:
+            n = max(b.numel() for name, b in self.named_buffers() if name.endswith("_q"))
+            self._scratch = torch.empty((n,), device=self.embed.device, dtype=torch.bfloat16)
+        return self._scratch
 
     def alloc_cache(self, B: int, L: int):
         c = self.c
@@ -149,13 +222,19 @@ class CausalLM(nn.Module):
         device positions ``pos0`` with ``lens = pos0 + 1`` valid keys; else prefill from 0."""
         B, T = tokens.shape
         x = self.embed.index_select(0, tokens.reshape(-1)).view(B, T, self.c.dim)
+        if self.quantized:
+            scratch = self._prefill_scratch(B * T)
+            for i, blk in enumerate(self.blocks):
+                x = blk(x, kcache[i], vcache[i], pos0, lens, decode, scratch)
+            return ops.linear_fp8(x[:, -1], self.lm_head_q, self.lm_head_s, rms_eps=self.c.eps, scratch=scratch)
         for i, blk in enumerate(self.blocks):
             x = blk(x, kcache[i], vcache[i], pos0, lens, decode)
         return ops.rms_linear(x[:, -1], self.norm, self.c.eps, self.lm_head)
 
     @torch.no_grad()
     def full_logits(self, tokens: torch.Tensor) -> torch.Tensor:
-        """Cache-free reference forward (all positions) -> [B, T, vocab] f32.  Test oracle."""
+        """Cache-free reference forward (all positions) -> [B, T, vocab] f32.  Test oracle; on a
+        quantised model it multiplies e4m3(q) * scale in fp32 (the gains are ones there)."""
         from ..ops import reference as R
         c = self.c
         B, T = tokens.shape
@@ -164,21 +243,22 @@ class CausalLM(nn.Module):
         pos = torch.arange(T, device=tokens.device)[None].expand(B, T)
         for blk in self.blocks:
             n = R.rms_norm(x, blk.attn_norm, c.eps).float()
-            qkv = (n @ blk.qkv.float().t()).view(B, T, c.heads + 2 * c.kv_heads, hd)
+            qkv = (n @ _weight_f32(blk, "qkv").t()).view(B, T, c.heads + 2 * c.kv_heads, hd)
             q = R.rope(qkv[:, :, :c.heads], pos, c.rope_theta).float()
             k = R.rope(qkv[:, :, c.heads:c.heads + c.kv_heads], pos, c.rope_theta).float()
             v = qkv[:, :, c.heads + c.kv_heads:]
             o = R.attention(q, k, v, causal=True).float()
-            x = x + o.reshape(B, T, -1) @ blk.o.float().t()
+            x = x + o.reshape(B, T, -1) @ _weight_f32(blk, "o").t()
             n = R.rms_norm(x, blk.mlp_norm, c.eps).float()
-            hg = n @ blk.gate_up.float().t()
+            hg = n @ _weight_f32(blk, "gate_up").t()
             h, g = hg.chunk(2, dim=-1)
-            x = x + (h * torch.nn.functional.silu(g)) @ blk.down.float().t()
+            x = x + (h * torch.nn.functional.silu(g)) @ _weight_f32(blk, "down").t()
         x = R.rms_norm(x, self.norm, c.eps).float()
-        return x @ self.lm_head.float().t()
+        return x @ _weight_f32(self, "lm_head").t()
 
 
 LM_NOISE = ("table", "philox")
+LM_WEIGHT_DTYPES = ("bf16", "fp8")
 BUCKETS = (1, 2, 4, 8)            # batch sizes of the philox decode path, capped at max_batch
 
 
@@ -225,9 +305,11 @@ class LMTextGenerator:
 
     def __init__(self, cfg: CausalLMConfig = TINY_LM, device=None, seed: int = 0, use_graphs: bool = True,
                  tokenizer=None, temperature: float = 0.8, top_k: int = 40, max_new_cap: int = 128,
-                 noise: str = "table", max_batch: int = 1) -> None:
+                 noise: str = "table", max_batch: int = 1, weight_dtype: str = "bf16") -> None:
         if noise not in LM_NOISE:
             raise ValueError(f"unknown lm noise {noise!r}: one of {', '.join(LM_NOISE)}")
+        if weight_dtype not in LM_WEIGHT_DTYPES:
+            raise ValueError(f"unknown lm weight dtype {weight_dtype!r}: one of {', '.join(LM_WEIGHT_DTYPES)}")
         if not 1 <= int(max_batch) <= BUCKETS[-1]:
             raise ValueError(f"max_batch must be 1..{BUCKETS[-1]}, not {max_batch}")
         if max_batch > 1 and noise != "philox":
@@ -256,6 +338,22 @@ class LMTextGenerator:
         if noise == "philox":
             # a reference sampler that reads its counters on the host cannot be captured
             self.use_graphs = self.use_graphs and ops.get_mode() == "hip"
+        self.weight_dtype = "bf16"
+        self.quant_ms = 0.0               # what quantize_fp8 took (with its one check of the scales)
+        if weight_dtype == "fp8":
+            self.quantize_fp8()
+
+    def quantize_fp8(self) -> None:
+        """The model's projections to weight-only fp8 (``CausalLM.quantize_fp8_``), after any
+        checkpoint is loaded and before the first call: a captured graph holds the bf16 weights."""
+        if self.buckets:
+            raise RuntimeError("quantize_fp8: quantise before the first generate call")
+        t0 = time.perf_counter()
+        self.model.quantize_fp8_()
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        self.quant_ms = (time.perf_counter() - t0) * 1e3
+        self.weight_dtype = "fp8"
 
     def _bucket(self, n: int) -> _Bucket:
         B = next(b for b in self.bucket_sizes if b >= n)

@@ -569,6 +569,79 @@ def rms_linear(x: torch.Tensor, gamma: torch.Tensor, eps: float, w: torch.Tensor
     return out.reshape(*x.shape[:-1], N)
 
 
+# ----------------------------------------------------------------------------- weight-only fp8 (LM decode)
+# The weight contract is the header comment of ops/csrc/lm_fp8.hip; ops.reference holds its model.
+FP8_GEMV_ROWS = 8            # linear_fp8: at most this many rows stream the codes (gemv_fp8_kernel)
+
+
+def quantize_rows_fp8(w: torch.Tensor, gamma: Optional[torch.Tensor] = None):
+    """bf16 w [Nw, K] (K % 16 == 0), with the RMSNorm gain gamma [K] folded in, -> (q uint8 [Nw, K]
+    OCP e4m3fn codes, scale fp32 [Nw]), one scale per row.  Raises on a row with a non-finite value
+    (its scale is not finite): the one check of the scales, with one small copy to the host."""
+    if w.dim() != 2 or w.shape[1] % 16:
+        raise ValueError(f"quantize_rows_fp8: w [Nw, K] with K % 16 == 0, not {tuple(w.shape)}")
+    if not _use_hip(w):
+        q, scale = ref.quantize_rows_fp8(w, gamma)
+    else:
+        w = w.to(torch.bfloat16).contiguous()
+        q = torch.empty(w.shape, device=w.device, dtype=torch.uint8)
+        scale = torch.empty((w.shape[0],), device=w.device, dtype=torch.float32)
+        ext().quant_rows_fp8(w, None if gamma is None else gamma.to(torch.bfloat16).contiguous(), q, scale)
+    if not bool(torch.isfinite(scale).all()):
+        raise ValueError("quantize_rows_fp8: a weight row holds a non-finite value")
+    return q, scale
+
+
+def dequantize_rows_fp8(q: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 [Nw, K] = bf16(e4m3(q) * scale[n]), into ``out`` (any contiguous bf16 buffer of at least
+    Nw * K elements: its first Nw * K are used) or a new tensor."""
+    n = q.numel()
+    if out is None:
+        out = torch.empty(q.shape, device=q.device, dtype=torch.bfloat16)
+    assert out.is_contiguous() and out.dtype == torch.bfloat16 and out.numel() >= n, "dequantize_rows_fp8: bad out"
+    o2 = out.view(-1)[:n].view(q.shape)
+    if not _use_hip(q):
+        return o2.copy_(ref.dequantize_rows_fp8(q, scale))
+    ext().dequant_rows_fp8(q, scale, o2)
+    return o2
+
+
+def linear_fp8(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None,
+               residual: Optional[torch.Tensor] = None, act: Optional[str] = None, rms_eps: Optional[float] = None,
+               out: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = act(r * scale * (x @ e4m3(q)^T) + bias) + residual over the quantised weight (q, scale) of
+    :func:`quantize_rows_fp8`; ``rms_eps``: r = rsqrt(mean x^2 + rms_eps) per row (an RMSNorm whose
+    gain is folded into q), else 1.  At most 8 rows stream the codes through the fp8 GEMV (the
+    decode path).  More rows (prefill) dequantise the weight into ``scratch`` (a contiguous bf16
+    buffer of at least q.numel() elements; else a new one) and run the bf16 GEMM, after an RMSNorm
+    with a gain of ones when ``rms_eps`` is given."""
+    K = x.shape[-1]
+    if K % 16 or q.shape[-1] != K:
+        raise ValueError(f"linear_fp8: K % 16 == 0 and q [Nw, K], not K = {K}, q {tuple(q.shape)}")
+    if not _use_hip(x):
+        y = ref.linear_fp8(x, q, scale, bias, residual, act, rms_eps)
+        return y if out is None else out.copy_(y.reshape(out.shape))
+    rows = x.numel() // K
+    N = q.shape[0] // 2 if act in ("geglu", "swiglu") else q.shape[0]
+    if rows > FP8_GEMV_ROWS:
+        w = dequantize_rows_fp8(q, scale, out=scratch)
+        if rms_eps is not None:
+            x = rms_norm(x, torch.ones(K, device=x.device, dtype=x.dtype), rms_eps)
+        return linear(x, w, bias, residual=residual, act=act, out=out)
+    x2 = x.reshape(rows, K)
+    if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    own = out is None
+    if own:
+        out = torch.empty((rows, N), device=x.device, dtype=x.dtype)
+    else:
+        assert out.numel() == rows * N and out.dtype in (torch.bfloat16, torch.float32), "linear_fp8: bad out"
+    o2 = out if out.dim() == 2 else out.view(rows, N)        # (a 2-D out may have strided rows)
+    r2 = residual.reshape(rows, N) if residual is not None else None
+    ext().gemv_fp8(x2, q, scale, bias, r2, o2, _ACT[act], -1.0 if rms_eps is None else float(rms_eps))
+    return out.view(*x.shape[:-1], N) if own else out
+
+
 # ----------------------------------------------------------------------------- causal-LM decode path
 def rope_kv(qkv: torch.Tensor, pos0: torch.Tensor, q_out: torch.Tensor, k_cache: torch.Tensor,
             v_cache: torch.Tensor, heads: int, kv_heads: int, theta: float) -> None:

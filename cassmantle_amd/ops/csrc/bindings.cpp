@@ -826,6 +826,68 @@ void rope_kv(const at::Tensor& qkv, const at::Tensor& pos0, at::Tensor& q_out, a
   launch_rope_kv(a, cur_stream());
 }
 
+// weight-only fp8 (lm_fp8.hip, weight contract there).  y = act(r * scale * (x @ e4m3(q)^T) + bias) + residual
+// for x [<= 8, K] (rows may be strided) and out [M, N] bf16 / fp32 (rows may be strided); rms_eps < 0: r = 1
+void gemv_fp8(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale, const c10::optional<at::Tensor>& bias,
+              const c10::optional<at::Tensor>& residual, at::Tensor& out, int64_t act, double rms_eps) {
+  CHECK_DEV(x); CHECK_BF16(x); CHECK_DEV(q); CHECK_CONTIG(q); CHECK_DEV(scale); CHECK_CONTIG(scale); CHECK_DEV(out);
+  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.size(0) >= 1 && x.size(0) <= 8, "gemv_fp8: x [1..8, K] rows contiguous");
+  TORCH_CHECK(q.dim() == 2 && q.scalar_type() == at::kByte && scale.scalar_type() == at::kFloat &&
+                  scale.numel() == q.size(0), "gemv_fp8: q uint8 [Nw, K], scale fp32 [Nw]");
+  TORCH_CHECK(out.dim() == 2 && out.stride(1) == 1 && out.size(0) == x.size(0) && out.stride(0) >= out.size(1),
+              "gemv_fp8: out [M, N] rows contiguous");
+  GemvFp8Args p;
+  p.A = bptr(x); p.lda = (int)x.stride(0);
+  p.Q = q.data_ptr<uint8_t>(); p.scale = scale.data_ptr<float>(); p.bias = opt_bptr(bias);
+  p.M = (int)x.size(0); p.K = (int)x.size(1); p.N = (int)out.size(1); p.act = (int)act;
+  p.ldc = (int)out.stride(0);
+  TORCH_CHECK(q.size(1) == p.K && p.K % 16 == 0 && p.K >= 16, "gemv_fp8: K mismatch or K % 16 != 0");
+  TORCH_CHECK(q.size(0) == ((act == 4 || act == 6) ? 2 * p.N : p.N) && p.N >= 1, "gemv_fp8: N mismatch");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0, "gemv_fp8: x and q rows must be 16-byte aligned");
+  if (bias.has_value() && bias->defined()) TORCH_CHECK(bias->numel() == q.size(0), "gemv_fp8: bias shape");
+  if (residual.has_value() && residual->defined()) {
+    CHECK_DEV(*residual); CHECK_BF16(*residual);
+    TORCH_CHECK(residual->dim() == 2 && residual->stride(1) == 1 && residual->size(0) == p.M && residual->size(1) == p.N,
+                "gemv_fp8: residual [M, N] rows contiguous");
+    p.residual = bptr(*residual); p.ldr = (int)residual->stride(0);
+  }
+  if (out.scalar_type() == at::kFloat) p.out_f32 = 1;
+  else CHECK_BF16(out);
+  p.C = out.data_ptr();
+  if (rms_eps >= 0.0) { p.rms = 1; p.rms_eps = (float)rms_eps; }
+  TORCH_CHECK(launch_gemv_fp8(p, cur_stream()), "gemv_fp8: shape not supported");
+}
+
+// q uint8 [rows, K], scale fp32 [rows] of w [rows, K] bf16 times the gain gamma [K] bf16 (optional)
+void quant_rows_fp8(const at::Tensor& w, const c10::optional<at::Tensor>& gamma, at::Tensor& q, at::Tensor& scale) {
+  CHECK_DEV(w); CHECK_BF16(w); CHECK_CONTIG(w); CHECK_DEV(q); CHECK_CONTIG(q); CHECK_DEV(scale); CHECK_CONTIG(scale);
+  TORCH_CHECK(w.dim() == 2 && w.size(1) % 16 == 0 && w.size(1) >= 16 && w.size(1) <= (1LL << 30),
+              "quant_rows_fp8: w [rows, K], K % 16 == 0");
+  TORCH_CHECK(q.scalar_type() == at::kByte && q.dim() == 2 && q.size(0) == w.size(0) && q.size(1) == w.size(1) &&
+                  scale.scalar_type() == at::kFloat && scale.numel() == w.size(0),
+              "quant_rows_fp8: q uint8 [rows, K], scale fp32 [rows]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "quant_rows_fp8: 16-byte aligned operands");
+  const uint16_t* g = opt_bptr(gamma);
+  if (g != nullptr)
+    TORCH_CHECK(gamma->numel() == w.size(1) && reinterpret_cast<uintptr_t>(g) % 16 == 0, "quant_rows_fp8: gamma [K], aligned");
+  launch_quant_rows_fp8(bptr(w), g, q.data_ptr<uint8_t>(), scale.data_ptr<float>(), w.size(0), (int)w.size(1),
+                        cur_stream());
+}
+
+// out bf16 [rows, K] = bf16(e4m3(q) * scale[row])
+void dequant_rows_fp8(const at::Tensor& q, const at::Tensor& scale, at::Tensor& out) {
+  CHECK_DEV(q); CHECK_CONTIG(q); CHECK_DEV(scale); CHECK_CONTIG(scale); CHECK_DEV(out); CHECK_CONTIG(out); CHECK_BF16(out);
+  TORCH_CHECK(q.dim() == 2 && q.scalar_type() == at::kByte && q.size(1) % 16 == 0 && q.size(1) <= (1LL << 30) &&
+                  scale.scalar_type() == at::kFloat && scale.numel() == q.size(0) && out.numel() == q.numel(),
+              "dequant_rows_fp8: q uint8 [rows, K] (K % 16 == 0), scale fp32 [rows], out bf16 [rows, K]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "dequant_rows_fp8: 16-byte aligned operands");
+  launch_dequant_rows_fp8(q.data_ptr<uint8_t>(), scale.data_ptr<float>(), bptr_mut(out), q.size(0), (int)q.size(1),
+                          cur_stream());
+}
+
 // what the two sampler entry points share: logits [B, V] (rows may be strided), the per-row state
 // step / tok [B] int64, pos / lens [B] int32, eos_bias [steps], out [steps, B]; `fn` names the caller
 static LmSampleArgs lm_sample_args(const char* fn, const at::Tensor& logits, const at::Tensor& eos_bias, int64_t eos,
@@ -1286,6 +1348,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("lm_sample", &lm_sample, nogil());
   m.def("lm_sample_seeded", &lm_sample_seeded, nogil());
   m.def("lm_gumbel", &lm_gumbel, nogil());
+  m.def("gemv_fp8", &gemv_fp8, nogil());
+  m.def("quant_rows_fp8", &quant_rows_fp8, nogil());
+  m.def("dequant_rows_fp8", &dequant_rows_fp8, nogil());
   m.def("cu_mask_stream", &cu_mask_stream);
   m.def("cu_count", &cu_count);
   m.def("softmax_rows", &softmax_rows, nogil());

@@ -167,6 +167,25 @@ struct DecodeArgs {
 };
 int decode_splits(int B, int Hk, int L);
 void launch_decode_attention(const DecodeArgs& a, int ns, hipStream_t s);
+// weight-only fp8 decode path (lm_fp8.hip; weight contract in its header comment)
+struct GemvFp8Args {
+  const uint16_t* A = nullptr; int lda = 0;   // raw bf16 activations [M][lda], lda % 8 == 0
+  const uint8_t* Q = nullptr;                 // e4m3 codes [Nw][K], K % 16 == 0, 16-byte aligned
+  const float* scale = nullptr;               // [Nw]
+  const uint16_t* bias = nullptr;             // [Nw] or null
+  const uint16_t* residual = nullptr; int ldr = 0;   // [M][ldr] or null
+  void* C = nullptr; int ldc = 0;             // [M][ldc] bf16 or fp32
+  int M = 0, N = 0, K = 0;                    // N outputs (gated: Nw = 2N, value row n and gate row N + n)
+  int act = 0, out_f32 = 0;
+  int rms = 0; float rms_eps = 0.f;           // rms: rows scaled by rsqrt(mean x^2 + rms_eps)
+};
+bool launch_gemv_fp8(const GemvFp8Args& p, hipStream_t s);   // false -> shape not handled (M > 8, K % 16, lda % 8)
+// q, scale of w [rows][K] bf16 times gamma [K] bf16 (null: no gain); K % 16 == 0
+void launch_quant_rows_fp8(const uint16_t* w, const uint16_t* gamma, uint8_t* q, float* scale, long long rows, int K,
+                           hipStream_t s);
+// out [rows][K] bf16 = bf16(e4m3(q) * scale[row])
+void launch_dequant_rows_fp8(const uint8_t* q, const float* scale, uint16_t* out, long long rows, int K,
+                             hipStream_t s);
 // decode-step sampler (lm_sample.hip): top-k of logits / T (+ EOS bias of the row's step) + Gumbel-max,
 // then token / position / length / step counter updated on the device; one workgroup per row, every
 // row with its own step counter.  The noise is either row `step` of a table (batch 1, seeds null) or

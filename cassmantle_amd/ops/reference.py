@@ -107,6 +107,66 @@ def rms_norm(x, weight, eps, dtype=None):
     return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * weight.to(xf.dtype)).to(dtype or x.dtype)
 
 
+# weight-only fp8 (the weight contract of ops/csrc/lm_fp8.hip's header comment, in torch)
+E4M3_MAX = 448.0
+
+
+def quantize_rows_fp8(w, gamma=None):
+    """w [Nw, K] (and the gain gamma [K] folded in) -> (q uint8 [Nw, K] e4m3fn codes, scale fp32
+    [Nw]): scale = rowmax |w * gamma| / 448 (1 for an all-zero row), q = RNE_e4m3(w * gamma /
+    scale), all in fp32.  A non-finite row gives a non-finite scale (ops.quantize_rows_fp8 raises)."""
+    if w.dim() != 2 or w.shape[1] % 16:
+        raise ValueError(f"quantize_rows_fp8: w [Nw, K] with K % 16 == 0, not {tuple(w.shape)}")
+    v = w.float()
+    if gamma is not None:
+        v = v * gamma.float()[None, :]
+    a = v.abs().amax(dim=1)
+    scale = torch.where(a == 0, torch.ones_like(a), a / torch.full_like(a, E4M3_MAX))   # (a true fp32 division)
+    r = (v / scale[:, None]).clamp(-E4M3_MAX, E4M3_MAX)
+    q = r.to(torch.float8_e4m3fn).view(torch.uint8)
+    return q.contiguous(), scale.contiguous()
+
+
+def e4m3_decode(q, dtype=None):
+    """uint8 e4m3fn codes -> their values (exact in bf16 and wider).  Off the CPU through a table of
+    the 256 codes made on the CPU, so the oracle does not lean on the device's own fp8 casts."""
+    if q.device.type == "cpu":
+        return q.view(torch.float8_e4m3fn).to(_ct(dtype))
+    lut = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).to(_ct(dtype)).to(q.device)
+    return lut[q.long()]
+
+
+def dequantize_rows_fp8(q, scale, dtype=None):
+    """W' = e4m3(q) * scale[n]: bf16 (one fp32 product, rounded) or unrounded in ``dtype``"""
+    if dtype is None:
+        return (e4m3_decode(q) * scale.float()[:, None]).to(torch.bfloat16)
+    return e4m3_decode(q, dtype) * scale.to(dtype)[:, None]
+
+
+def linear_fp8(x, q, scale, bias=None, residual=None, act=None, rms_eps=None, out_dtype=None, dtype=None):
+    """y = act(r * scale * (x @ e4m3(q)^T) + bias) + residual, r = rsqrt(mean x^2 + rms_eps) per
+    row when ``rms_eps`` is given (the gain lives in q), else 1.  Gated acts: value row n, gate
+    row N + n."""
+    if x.shape[-1] % 16:
+        raise ValueError(f"linear_fp8: K % 16 == 0, not K = {x.shape[-1]}")
+    od = out_dtype or dtype or x.dtype
+    ct = _ct(dtype)
+    xf = x.to(ct)
+    y = torch.matmul(xf, e4m3_decode(q, ct).t()) * scale.to(ct)
+    if rms_eps is not None:
+        y = y * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + rms_eps)
+    if bias is not None:
+        y = y + bias.to(ct)
+    if act in ("geglu", "swiglu"):
+        h, g = y.chunk(2, dim=-1)
+        y = h * (F.gelu(g) if act == "geglu" else F.silu(g))
+    else:
+        y = _act(y, act)
+    if residual is not None:
+        y = y + residual.to(ct)
+    return y.to(od)
+
+
 def rope(x, pos, theta, dtype=None):
     """Rotate-half rotary embedding.  x [B, T, h, d]; pos [B, T] int positions."""
     d = x.shape[-1]

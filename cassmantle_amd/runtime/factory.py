@@ -274,7 +274,7 @@ def build_prompt_generator(cfg: Config, device: Optional[str] = None):
     m = cfg.model
     if m.prompt_generator == "lm":
         from ..game.prompts import BatchingPromptGenerator, LMPromptGenerator
-        from ..models.lm import LM_CONFIGS, LM_NOISE, LMTextGenerator, SentencePieceTokenizer
+        from ..models.lm import LM_CONFIGS, LM_NOISE, LM_WEIGHT_DTYPES, LMTextGenerator, SentencePieceTokenizer
         # bad LM flags raise here, not at the first round
         if m.lm_noise not in LM_NOISE:
             raise ValueError(f"unknown lm_noise {m.lm_noise!r}: one of {', '.join(LM_NOISE)}")
@@ -282,12 +282,18 @@ def build_prompt_generator(cfg: Config, device: Optional[str] = None):
             raise ValueError(f"lm_batch_max must be 1..8, not {m.lm_batch_max}")
         if m.lm_batch_max > 1 and m.lm_noise != "philox":
             raise ValueError("lm_batch_max > 1 needs lm_noise=philox (the noise table is batch 1)")
+        if m.lm_weight_dtype not in LM_WEIGHT_DTYPES:
+            raise ValueError(f"unknown lm_weight_dtype {m.lm_weight_dtype!r}: one of {', '.join(LM_WEIGHT_DTYPES)}")
         tok = SentencePieceTokenizer(m.lm_tokenizer) if m.lm_tokenizer else None
+        # a checkpoint loads into the bf16 projections; they are quantised after it
         gen = LMTextGenerator(LM_CONFIGS[m.lm_model], device=device, seed=m.seed, use_graphs=m.use_graphs,
-                              tokenizer=tok, noise=m.lm_noise, max_batch=int(m.lm_batch_max))
+                              tokenizer=tok, noise=m.lm_noise, max_batch=int(m.lm_batch_max),
+                              weight_dtype="bf16" if m.lm_weights else m.lm_weight_dtype)
         if m.lm_weights:
             from ..models.weights import load_causal_lm, read_safetensors
             load_causal_lm(gen.model, read_safetensors(m.lm_weights))
+            if m.lm_weight_dtype == "fp8":
+                gen.quantize_fp8()
         pg = LMPromptGenerator(gen)
         if m.lm_batch_max > 1:
             # the rooms of this process ask at the same moment of the shared round clock: one LM batch

@@ -3,8 +3,11 @@
     python tools/bench_lm.py --model mistral-7b --new 96 --prompt-len 64
     python tools/bench_lm.py --model mistral-7b --new 96 --prompt-len 64 --noise philox --batch 8
     python tools/bench_lm.py --model mistral-7b --new 96 --prompt-len 64 --parent /path/to/built/parent
+    python tools/bench_lm.py --model mistral-7b --new 96 --prompt-len 64 --noise philox --batch 8 --weights fp8
 
-Prints one JSON line.  Without --batch / --noise / --parent: batch 1 with the noise table, ms/token,
+Prints one JSON line.  --weights bf16 | fp8 (this tree only): the projections as they are or quantised
+to weight-only fp8 at load; the record gains the weight bytes a step streams, the TB/s they imply
+and the quantisation time.  Without --batch / --noise / --parent / --weights: batch 1 with the noise table, ms/token,
 tokens/s and the HBM-bandwidth bound (weights bytes / 8 TB/s).  With one of them the record holds
 what batching changes: decode ms per step, tokens/s summed over the batch, prefill ms, the host ms a
 call spends before its first launch (the noise table, in the table path) and the whole call.
@@ -46,8 +49,11 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="sequences decoded as one batch (needs --noise philox above 1)")
     ap.add_argument("--noise", choices=("table", "philox"), default=None)
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit to import the package from")
+    ap.add_argument("--weights", choices=("bf16", "fp8"), default=None,
+                    help="projection weights: bf16, or weight-only fp8 quantised at load (the record gains weight_bytes, "
+                         "weight_tb_per_s and quantize_ms)")
     a = ap.parse_args()
-    extended = a.batch is not None or a.noise is not None or a.parent is not None
+    extended = a.batch is not None or a.noise is not None or a.parent is not None or a.weights is not None
     root = os.path.abspath(a.parent) if a.parent else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, root)
 
@@ -57,6 +63,8 @@ def main():
     B, noise = a.batch or 1, a.noise or "table"
     cfg = LM_CONFIGS[a.model]
     kw = {"noise": noise, "max_batch": B} if extended else {}
+    if a.weights is not None:
+        kw["weight_dtype"] = a.weights
     t0 = time.time()
     g = LMTextGenerator(cfg, device="cuda", use_graphs=not a.no_graphs, max_new_cap=max(a.new, 8), **kw)
     torch.cuda.synchronize()
@@ -105,13 +113,20 @@ def main():
                           "decode_tokens_per_s": round(1e3 / ms_tok, 1), "hbm_bound_ms_per_token": round(bound_ms, 3),
                           "graphs": not a.no_graphs}))
         return
-    print(json.dumps({"model": cfg.name, "params": params, "tree": "parent" if a.parent else "this", "noise": noise,
-                      "batch": B, "init_s": round(init_s, 2), "prompt_len": a.prompt_len, "new_tokens": a.new,
-                      "decode_ms_per_step": round(ms_tok, 3), "decode_tokens_per_s": round(B * 1e3 / ms_tok, 1),
-                      "prefill_ms": round(t_one * 1e3 - host_one - ms_tok, 2),
-                      "host_ms_before_first_launch": round(host_all, 2), "call_ms": round(t_all * 1e3, 2),
-                      "call_ms_per_sequence": round(t_all * 1e3 / B, 2),
-                      "hbm_bound_ms_per_token": round(bound_ms, 3), "graphs": not a.no_graphs}))
+    rec = {"model": cfg.name, "params": params, "tree": "parent" if a.parent else "this", "noise": noise,
+           "batch": B, "init_s": round(init_s, 2), "prompt_len": a.prompt_len, "new_tokens": a.new,
+           "decode_ms_per_step": round(ms_tok, 3), "decode_tokens_per_s": round(B * 1e3 / ms_tok, 1),
+           "prefill_ms": round(t_one * 1e3 - host_one - ms_tok, 2),
+           "host_ms_before_first_launch": round(host_all, 2), "call_ms": round(t_all * 1e3, 2),
+           "call_ms_per_sequence": round(t_all * 1e3 / B, 2),
+           "hbm_bound_ms_per_token": round(bound_ms, 3), "graphs": not a.no_graphs}
+    if a.weights is not None:
+        # the bytes a decode step streams (every projection; codes and scales when quantised) and the
+        # rate they imply; with fp8 "params" counts what is left in bf16 (embed, the gains)
+        wb = g.model.weight_bytes()
+        rec.update({"weights": a.weights, "weight_bytes": wb, "weight_tb_per_s": round(wb / (ms_tok * 1e-3) / 1e12, 3),
+                    "quantize_ms": round(g.quant_ms, 1), "hbm_bound_ms_per_token": round(wb / 8.0e12 * 1e3, 3)})
+    print(json.dumps(rec))
 
 
 if __name__ == "__main__":
