@@ -852,8 +852,8 @@ __global__ void __launch_bounds__(256) attn_fp8_pack_kernel(AttnArgs a, int Hk, 
     unpack8(kv, kf);
     unpack8(vv, vf);
     *reinterpret_cast<uint2*>(K8 + (bh * Nkp + key) * 64 + ch * 8) =
-        make_uint2(f8x4(kf[0], kf[1], kf[2], kf[3]), f8x4(kf[4], kf[5], kf[6], kf[7]));
-    const uint32_t v0 = f8x4(vf[0], vf[1], vf[2], vf[3]), v1 = f8x4(vf[4], vf[5], vf[6], vf[7]);
+        make_uint2(f8x4_sat(kf[0], kf[1], kf[2], kf[3]), f8x4_sat(kf[4], kf[5], kf[6], kf[7]));
+    const uint32_t v0 = f8x4_sat(vf[0], vf[1], vf[2], vf[3]), v1 = f8x4_sat(vf[4], vf[5], vf[6], vf[7]);
     const int slot = f8_slot(kk);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {

@@ -40,6 +40,16 @@ CM_DEVICE uint32_t f8x4(float a, float b, float c, float d) {
   return w;
 }
 
+// the K/V emitters' form (attn_fp8_pack_kernel, the GEMM epilogues' GemmArgs::kv8): saturating.  The
+// conversion itself returns the NaN code 0x7F / 0xFF for a finite input that rounds above 448, so the
+// values are clamped to +-448 first (one v_med3_f32 each) and come out as 0x7E / 0xFE, as the
+// attention oracle's e4m3 model has it.  Q and P of the attention loop keep f8x4: the kernel bounds
+// their range itself.
+CM_DEVICE uint32_t f8x4_sat(float a, float b, float c, float d) {
+  return f8x4(__builtin_amdgcn_fmed3f(a, -448.f, 448.f), __builtin_amdgcn_fmed3f(b, -448.f, 448.f),
+              __builtin_amdgcn_fmed3f(c, -448.f, 448.f), __builtin_amdgcn_fmed3f(d, -448.f, 448.f));
+}
+
 // slot of key offset kk (0..63) inside its 64-key block of the fp8 attention kernel's V8t image
 // (attention.hip: slot 32h + j of a block holds the key of S accumulator register j&15 of key
 // half j>>4 in lane half h)
@@ -56,7 +66,7 @@ CM_DEVICE bool kv8_store4(const Args& p, int m, int n, const float* o) {
   if (p.kv8 == nullptr || n < p.kv8_col0) return false;
   const int C = p.kv8_hk * 64, rel = n - p.kv8_col0;
   const int b = m / p.kv8_ntok, key = m - b * p.kv8_ntok;
-  const uint32_t w = f8x4(o[0], o[1], o[2], o[3]);
+  const uint32_t w = f8x4_sat(o[0], o[1], o[2], o[3]);
   if (rel < C) {
     const long long bh = (long long)b * p.kv8_hk + (rel >> 6);
     *reinterpret_cast<uint32_t*>(p.kv8 + (bh * p.kv8_ntok + key) * 64 + (rel & 63)) = w;

@@ -313,7 +313,7 @@ CM_DEVICE void tile_epilogue(const GemmArgs& p, f32x4_t (&acc)[TI][TJ], uint4* s
             const int rel = n - p.kv8_col0, b = m / p.kv8_ntok, key = m - b * p.kv8_ntok;
             const long long bh = (long long)b * p.kv8_hk + (rel >> 6);
             *reinterpret_cast<uint2*>(p.kv8 + (bh * p.kv8_ntok + key) * 64 + (rel & 63)) =
-                make_uint2(f8x4(a[0], a[1], a[2], a[3]), f8x4(a[4], a[5], a[6], a[7]));
+                make_uint2(f8x4_sat(a[0], a[1], a[2], a[3]), f8x4_sat(a[4], a[5], a[6], a[7]));
           }                                            // V: transposed pass below
           return v;
         }
@@ -367,7 +367,7 @@ CM_DEVICE void tile_epilogue(const GemmArgs& p, f32x4_t (&acc)[TI][TJ], uint4* s
                 const int kk = 32 * (jj >> 4) + (jj & 3) + 8 * ((jj & 15) >> 2) + 4 * h;
                 f[e] = bf2f(T[(kb * 64 + kk) * OST + col]);
               }
-              w[q4] = f8x4(f[0], f[1], f[2], f[3]);
+              w[q4] = f8x4_sat(f[0], f[1], f[2], f[3]);
             }
             const int b = mb / p.kv8_ntok, key0 = mb - b * p.kv8_ntok;
             const long long bh = (long long)b * p.kv8_hk + ((n - vc0) >> 6);

@@ -122,9 +122,14 @@ def quantize_rows_fp8(w, gamma=None):
         v = v * gamma.float()[None, :]
     a = v.abs().amax(dim=1)
     scale = torch.where(a == 0, torch.ones_like(a), a / torch.full_like(a, E4M3_MAX))   # (a true fp32 division)
-    r = (v / scale[:, None]).clamp(-E4M3_MAX, E4M3_MAX)
-    q = r.to(torch.float8_e4m3fn).view(torch.uint8)
-    return q.contiguous(), scale.contiguous()
+    return e4m3_encode(v / scale[:, None]).contiguous(), scale.contiguous()
+
+
+def e4m3_encode(t):
+    """values -> uint8 OCP e4m3fn codes: fp32, clamped to +-448 (saturating), then round to nearest
+    even by torch's cast (subnormals down to 2^-9 included, -0.0 keeps its sign).  The oracle
+    calls it on CPU tensors only, so that it does not lean on the device's own fp8 casts."""
+    return t.float().clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
 
 
 def e4m3_decode(q, dtype=None):

@@ -1,6 +1,7 @@
 """Instruments for localised kernel errors, shared by test_kernel_oracle.py (CPU: the instruments
-themselves, proven on planted bugs) and test_kernel_edges_gpu.py, test_kernel_edges_conv_gpu.py,
-test_kernel_edges_decode_gpu.py and test_kernel_edges_scorer_gpu.py (the HIP kernels).
+themselves, proven on planted bugs; test_kv8_oracle.py: the fp8 K/V image model) and
+test_kernel_edges_gpu.py, test_kernel_edges_conv_gpu.py, test_kernel_edges_decode_gpu.py,
+test_kernel_edges_scorer_gpu.py and test_kernel_edges_kv8_gpu.py (the HIP kernels).
 
 A whole-tensor ``|out - ref| / |ref|`` under 1e-2 passes a kernel that drops the bias of one row,
 leaves one padding key unmasked or normalises one row group with another's statistics.  Three
@@ -46,6 +47,12 @@ test_kernel_oracle.py::test_floor_table prints with ``-s``):
     M = 8 | 9 ln_linear   one row                    1.5e-2   2.80e-3   (4 columns: 8.1e-3 at M = 8, so the row)
     decode, d = 128 / L > 4096   one query x d       2e-2     8.93e-3   (with a bf16 P)
     mean_pool_l2          one row                    1e-5     1.39e-7   (the fp32 evaluation; fp32 output)
+    fp8 K/V image (kv8)   16 keys x d of one head    6e-2     2.88e-2   (the one-rounding writer only, see below)
+
+The e4m3 K/V image of the fp8 attention kernel has a byte-exact CPU model (:func:`kv8_image_model`):
+the pack and the LDS-staged GEMM epilogue convert bf16 values and must equal it byte for byte
+(test_kernel_edges_kv8_gpu.py).  Only the A-in-registers epilogue, which rounds its fp32
+accumulators to e4m3 once, is held to a bound, the ``kv8`` row: twice the worst block of e4m3(y64).
 
 The GEMV keeps the kernel's own block, one row x the columns of one thread block: the bf16 store
 alone stays under half of 1e-2 there.  The four cosine kernels are held to an absolute 1e-5
@@ -529,11 +536,17 @@ def attention64(q, k, v, lens=None, causal=False, scale=None) -> torch.Tensor:
     return out
 
 
-def ideal_attention(q, k, v, lens=None, causal=False, scale=None, fp8=False, drop_last=False, extra_key=False):
+def ideal_attention(q, k, v, lens=None, causal=False, scale=None, fp8=False, drop_last=False, extra_key=False,
+                    kv8=None):
     """flash attention in fp64 with the kernels' roundings: Q * scale * log2(e) and the
     unnormalised P = 2^(S - max) in bf16 (e4m3 for fp8, as K and V).  The planted bugs:
-    ``drop_last`` masks the last valid key, ``extra_key`` lets the first masked one in."""
+    ``drop_last`` masks the last valid key, ``extra_key`` lets the first masked one in.
+    ``kv8`` (with fp8): a K/V image (:func:`kv8_image_model`) whose decoded bytes stand in for
+    e4m3(k) and e4m3(v), as the fp8 kernel reads them; k and v then give the shapes only."""
     B, Nq, H, d = q.shape
+    if kv8 is not None:
+        assert fp8
+        k, v = (t[:, :k.shape[1]] for t in kv8_unpack(kv8, B, k.shape[1], k.shape[2]))
     g = H // k.shape[2]
     scale = d ** -0.5 if scale is None else scale
     rq = e4m3 if fp8 else (lambda t: bf16_round(t).to(F64))
@@ -558,6 +571,120 @@ def ideal_attention(q, k, v, lens=None, causal=False, scale=None, fp8=False, dro
         o = torch.where(l > 0, (p @ vb) / l.clamp_min(1e-300), torch.zeros_like(l))
         out[b] = o.permute(1, 0, 2)
     return bf16_round(out)
+
+
+# ------------------------------------------------------------------------------ the fp8 K/V image
+# K8 [B][Hk][Nkp][64] then V8t [B][Hk][64][Nkp] (Nkp: keys rounded up to 64), OCP e4m3 bytes, every
+# key at or past min(Nk, lens[b]) zero, every 64-key block of a V8t row in slot order (attention.hip's
+# header comment).  Two writers: attn_fp8_pack_kernel and the GEMM epilogues (GemmArgs::kv8).
+BOUND["kv8"] = 6e-2          # decoded image against fp64 K/V per 16 keys x 64 d of one head: twice the worst block of
+#                              e4m3(y64) on the KV8_AREG_C cases (2.88e-2, test_kernel_oracle.py::test_ideal_kv8_writer)
+KV8_BLOCK = (1, 16, 1, None)
+CANARY = PATTERN[1]          # the byte of a guarded uint8 buffer: -0.203 in e4m3, small and finite
+KV8_PACK_CASES = ([(3, Nk, 2, lens) for Nk in ATTN_NK for lens in ((Nk, 1, 0), None)] +      # (B, Nk, Hk, lens)
+                  [(3, 65, Hk, (65, 1, 0)) for Hk in (1, 3)])
+# (images, tokens per image) of the QKV GEMM at C = 192: Hk = 3, N = 576, K = 192, K columns from
+# 192, V columns from 384.  M = 192: one full BM = 128 tile and a partial one of exactly one key
+# block, three images in a BM = 256 tile; M = 384: an image boundary inside a tile of either BM.
+# BN = 256, 160 and 80 straddle Q|K and K|V and end in a partial tile, 128 straddles Q|K, 64 is aligned
+KV8_EPI_GEOMS = ((3, 64), (2, 192))
+KV8_EPI_C = 192
+KV8_SPLIT_K = 512            # a forced (cfg, 2) needs eight k-tiles to be a plan (gemm_cases); kv8 then runs it unsplit
+KV8_AREG_C = (320, 640)      # the A-in-registers writer, geometry KV8_EPI_GEOMS[0]
+
+
+def kv8_key(slot):
+    """key offset (0..63) that slot 32h + j of a 64-key block holds:
+    kappa(h, j) = 32(j>>4) + (j&3) + 8((j&15)>>2) + 4h"""
+    h, j = slot >> 5, slot & 31
+    return 32 * (j >> 4) + (j & 3) + 8 * ((j & 15) >> 2) + 4 * h
+
+
+def kv8_slot(kk):
+    """slot of key offset kk (0..63), kappa inverted bit by bit: kk>>5 is j>>4, kk&3 is j&3,
+    (kk>>3)&3 is (j&15)>>2 and (kk>>2)&1 is h"""
+    return 32 * ((kk >> 2) & 1) + 16 * (kk >> 5) + 4 * ((kk >> 3) & 3) + (kk & 3)
+
+
+def kv8_key_halves_swapped(slot):
+    """planted: kappa with the lane-half bit h and the key-half bit j>>4 exchanged"""
+    h, j = slot >> 5, slot & 31
+    return 32 * h + (j & 3) + 8 * ((j & 15) >> 2) + 4 * (j >> 4)
+
+
+def kv8_image_model(k, v, lens=None, key_of_slot=kv8_key, zero_past_lens=True) -> torch.Tensor:
+    """the flat uint8 image of bf16 k, v [B, Nk, Hk, 64] on the CPU: ref.e4m3_encode of every
+    valid key (fp32, saturating at +-448, round to nearest even, subnormals included), 0x00 for
+    every key from min(Nk, lens[b]) to Nkp.  test_kernel_edges_kv8_gpu.py holds the emitters to
+    that rule over all of bf16.  On an MI355X v_cvt_pk_fp8_f32 agrees with the CPU cast on every
+    finite bf16 value up to 464 in magnitude (subnormals, ties, both zeros; 450 .. 464 round down
+    to 448), and returns the NaN code 0x7F / 0xFF from 466 on: it does not saturate, so the
+    emitters clamp to +-448 first (f8x4_sat in common.h).  The planted bugs: ``key_of_slot``
+    (another order of a block's keys), ``zero_past_lens=False`` (keys past lens converted like
+    the others)."""
+    B, Nk, Hk, d = k.shape
+    assert d == 64 and v.shape == k.shape
+    Nkp = (Nk + 63) // 64 * 64
+    kz, vz = torch.zeros(2, B, Nkp, Hk, 64, dtype=torch.uint8)
+    for b in range(B):
+        n = Nk if lens is None or not zero_past_lens else min(Nk, int(lens[b]))
+        kz[b, :n], vz[b, :n] = ref.e4m3_encode(k[b, :n].cpu()), ref.e4m3_encode(v[b, :n].cpu())
+    idx = torch.arange(Nkp)
+    src = (idx & ~63) + key_of_slot(idx & 63)
+    return torch.cat([kz.permute(0, 2, 1, 3).flatten(), vz[:, src].permute(0, 2, 3, 1).flatten()])
+
+
+def kv8_views(image, B, Nk, Hk):
+    """K8 [B, Hk, Nkp, 64] and V8t [B, Hk, 64, Nkp] of a flat image (views)"""
+    Nkp = (Nk + 63) // 64 * 64
+    half = B * Hk * Nkp * 64
+    assert image.numel() == 2 * half
+    return image[:half].view(B, Hk, Nkp, 64), image[half:].view(B, Hk, 64, Nkp)
+
+
+def kv8_unpack(image, B, Nk, Hk):
+    """fp64 K and V [B, Nkp, Hk, 64] of an image, the keys back in their natural order"""
+    K8, V8t = kv8_views(image.cpu(), B, Nk, Hk)
+    idx = torch.arange(K8.shape[2])
+    dst = (idx & ~63) + kv8_slot(idx & 63)
+    return (ref.e4m3_decode(K8, F64).permute(0, 2, 1, 3).contiguous(),
+            ref.e4m3_decode(V8t, F64)[..., dst].permute(0, 3, 1, 2).contiguous())
+
+
+def kv8_stale_run(image, B, Nk, Hk, b=0, h=0, d=5, run=1) -> torch.Tensor:
+    """planted: a copy of the image in which one 16-slot run of one V8t row was never written"""
+    bug = image.clone()
+    kv8_views(bug, B, Nk, Hk)[1][b, h, d, 16 * run:16 * run + 16] = CANARY
+    return bug
+
+
+def kv8_neighbour_head(image, B, Nk, Hk, h=1) -> torch.Tensor:
+    """planted: the V bytes of head h (the last 64 columns of a column tile) taken from head h - 1"""
+    bug = image.clone()
+    V8t = kv8_views(bug, B, Nk, Hk)[1]
+    V8t[:, h] = V8t[:, h - 1].clone()
+    return bug
+
+
+def kv8_codes_apart(a, b) -> int:
+    """the largest distance of two images' bytes in e4m3 codes: sign-magnitude order, both zeros equal"""
+    def ordinal(t):
+        i = t.cpu().to(torch.int64)
+        return torch.where(i >= 128, -(i & 127), i)
+    return int((ordinal(a) - ordinal(b)).abs().max())
+
+
+def kv8_epi_inputs(geom, C=KV8_EPI_C, K=None):
+    """x [B * ntok, K], ln gamma, ln beta, w [3C, K], bias of the QKV projection"""
+    B, ntok = geom
+    K = C if K is None else K
+    return ln_fold_inputs(B * ntok, 3 * C, K, seed=500 + B * ntok + C + K)
+
+
+def qkv_split(y, geom, C):
+    """[M, 3C] -> Q [M, C], K and V [B, ntok, C // 64, 64]"""
+    B, ntok = geom
+    return y[:, :C], y[:, C:2 * C].reshape(B, ntok, C // 64, 64), y[:, 2 * C:].reshape(B, ntok, C // 64, 64)
 
 
 DECODE_L = (1, 127, 128, 129)

@@ -574,6 +574,22 @@ def test_mean_pool_that_reads_one_token_of_an_empty_row_fails():
         assert block_rel_err(ko.mean_pool64(h, lens), y64, (1, None)) == 0.0
 
 
+def test_ideal_kv8_writer():
+    """the ideal single-rounding writer of the fp8 K/V image, e4m3(y64), on the A-in-registers cases
+    of test_kernel_edges_kv8_gpu.py: BOUND["kv8"] is twice its worst 16-key x 64-d block, rounded up
+    to one digit (the bf16-then-e4m3 writers are byte-exact against the model and need no bound)"""
+    geom = ko.KV8_EPI_GEOMS[0]
+    worst = 0.0
+    for C in ko.KV8_AREG_C:
+        y64 = ko.ln_linear64(*ko.kv8_epi_inputs(geom, C))
+        for t in ko.qkv_split(y64, geom, C)[1:]:
+            e = block_rel_err(ko.e4m3(t), t, ko.KV8_BLOCK)
+            worst = max(worst, e)
+            floor("kv8", e, C)
+    digit = 10.0 ** math.floor(math.log10(2 * worst))
+    assert BOUND["kv8"] == pytest.approx(math.ceil(2 * worst / digit) * digit, rel=1e-12), worst
+
+
 def test_glue_instruments():
     x = ko.all_bf16()
     assert x.numel() == 65282 and torch.isinf(x[-2:].float()).all() and x[:-2].unique().numel() == 65279   # (-0.0 == 0.0)
