@@ -752,6 +752,7 @@ __global__ void __launch_bounds__(64 * NW, 2) attn16_d40_kernel(AttnArgs a) {
 template <int NW>
 void launch_a16(const AttnArgs& a, hipStream_t s) {
   const int nqb = (a.Nq + 32 * NW - 1) / (32 * NW);
+  attention_note_kernel(kAttnA16, 48, 48, NW);
   hipLaunchKernelGGL((attn16_d40_kernel<NW>), dim3(nqb * a.H * a.B), dim3(64 * NW), 0, s, a);
 }
 
@@ -761,6 +762,7 @@ void launch_t(const AttnArgs& a, hipStream_t s) {
   constexpr int QB = 32 * NW;
   int nqb = (a.Nq + QB - 1) / QB;
   dim3 grid(nqb * a.H * a.B);
+  attention_note_kernel(kAttnFwd, DQK, DO, NW);
   // K/V double-buffered in LDS (level-1 self-attention 247 -> 240 us, 568.7 -> 566.7 ms/step
   // same box x3, profiles/r2_attn_db_ab.txt; the single-buffer variant was removed in round 4)
   auto* kfn = &attn_fwd_kernel<DQK, DO, NW, true>;
@@ -775,6 +777,15 @@ void launch_t(const AttnArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(kfn, grid, dim3(64 * NW), 2 * G::LDS_BYTES, s, a);
 }
 
+// Which test holds which branch (tests/test_kernel_edges_gpu.py; each asserts attention_last_kernel):
+//   8 waves (DO <= 96, 1024 blocks of 256 queries)   test_attention_wide_grid_edges: 32/32, 64/64 (GQA, causal),
+//                                                    80/96, 96/96 and 48/64 (causal d = 40, the MF path)
+//   4 waves by the 512-block rule                    test_attention_wide_grid_edges: 64/64 at Nq = 33 (three idle waves)
+//   4 waves by the Nq >= 256 rule                    the Nq = 257 cases of test_attention_generic_edges /
+//                                                    _roundup_edges / _lm_prefill_edges (128/128, GQA, causal) and the
+//                                                    48/64 rows of test_attention_wide_grid_edges
+//   2 waves                                          every other case of those tests (Nq = 1, 33, 65)
+// launch_attention's round-up branch (d < DQK) and the 96/96 and 128/128 widths: test_attention_roundup_edges
 template <int DQK, int DO>
 void launch_nw(const AttnArgs& a, hipStream_t s) {
   // enough workgroups to fill 256 CUs: fall back to fewer waves per block for short sequences
@@ -1208,6 +1219,7 @@ attn_fp8_kernel(AttnArgs a, int Hk, int Nkp, const uint8_t* __restrict__ K8, con
 template <int NQ, int NS>
 void launch_fp8_t(const AttnArgs& a, int Hk, int Nkp, const uint8_t* K8, const uint8_t* V8t, hipStream_t s) {
   const int nqb = (a.Nq + 32 * NQ - 1) / (32 * NQ);
+  attention_note_kernel(kAttnFp8, a.d, a.d, NQ * NS);
   // two LDS stages on the 2-split blocks unless CASSMANTLE_FP8_DBUF=0 (A/B knob; =2 forces every
   // variant).  Same box (profiles/r5_fp8_attn_dbuf_ab.txt): 2x2 self-attention 1.0-1.6 % faster,
   // 4x2 3-5 %; the one-step cross-attention blocks (NS 1) +1 %, the 80 KB 1x4 stages 12-30 % slower
@@ -1266,6 +1278,15 @@ void launch_attention_fp8(const AttnArgs& a, int Hk, uint8_t* ws, hipStream_t s,
     case 24: return launch_fp8_t<2, 4>(a, Hk, Nkp, K8, V8t, s);
     default: return launch_fp8_t<4, 1>(a, Hk, Nkp, K8, V8t, s);
   }
+}
+
+// per calling thread, as gemm.hip's g_last_plan (the generation and the scorer thread both launch)
+static thread_local int g_last_attn[4] = {-1, 0, 0, 0};
+void attention_note_kernel(AttnFamily family, int dqk, int dout, int nw) {
+  g_last_attn[0] = family; g_last_attn[1] = dqk; g_last_attn[2] = dout; g_last_attn[3] = nw;
+}
+void attention_last_kernel(int* family, int* dqk, int* dout, int* nw) {
+  *family = g_last_attn[0]; *dqk = g_last_attn[1]; *dout = g_last_attn[2]; *nw = g_last_attn[3];
 }
 
 // d = 40 kernel: 1 = 16x16-block kernel, 0 = the 32x32x16 kernel, -1 = CASSMANTLE_ATTN16 (default 1)

@@ -337,6 +337,7 @@ void launch_attention_d512(const AttnArgs& a, float* ws, hipStream_t s) {
     return true;
   }();
   (void)once;
+  attention_note_kernel(kAttnD512, D5, D5, NW5);
   const int ns = ws ? d512_splits(a) : 1;
   int kps = (a.Nk + ns - 1) / ns;
   kps = (kps + KT5 - 1) / KT5 * KT5;

@@ -1340,6 +1340,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("dcopy", &dcopy, nogil());
   m.def("set_fp8_attn_variant", [](int64_t v) { set_fp8_attn_variant((int)v); });
   m.def("set_attn_d40_variant", [](int64_t v) { set_attn_d40_variant((int)v); });
+  m.def("attention_last_kernel", []() {
+    static const char* const names[] = {"fwd", "a16", "fp8", "d512"};
+    int f, dqk, dout, nw;
+    attention_last_kernel(&f, &dqk, &dout, &nw);
+    return py::make_tuple(f >= 0 && f < 4 ? names[f] : "none", dqk, dout, nw);
+  });
   m.def("gemm_set_raster", &gemm_set_raster);
   m.def("latent_step", &latent_step, nogil());
   m.def("advance_step", &advance_step, nogil());

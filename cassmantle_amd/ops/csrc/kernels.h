@@ -103,6 +103,12 @@ struct AttnArgs {
   int group = 1;                  // query heads per K/V head (GQA)
 };
 void launch_attention(const AttnArgs& a, hipStream_t s);
+// the attention kernel the calling thread launched last (as gemm_last_plan): the family, the
+// template widths of QK^T and P.V (fp8 / d512: the head dim) and the waves per block.  Written by
+// every attention launcher, so it is never stale
+enum AttnFamily { kAttnFwd, kAttnA16, kAttnFp8, kAttnD512 };
+void attention_note_kernel(AttnFamily family, int dqk, int dout, int nw);
+void attention_last_kernel(int* family, int* dqk, int* dout, int* nw);
 // head dim 512 (VAE mid-block): flash kernel; ws = attention_d512_workspace bytes (key-split
 // partials for short grids, 0 otherwise)
 long long attention_d512_workspace(const AttnArgs& a);

@@ -35,6 +35,7 @@ test_kernel_oracle.py::test_floor_table prints with ``-s``):
     LayerNorm fold        16 rows x 16 columns       1.5e-2   3.98e-3
     GroupNorm fold        16 rows x 16 columns       1e-2     2.73e-3
     attention (bf16)      16 queries x d             2e-2     3.36e-3
+    attention, dispatch   16 queries x d             2e-2     5.99e-3   (every instantiation, below; the worst: d = 128, GQA)
     attention (fp8)       16 queries x d             0.12     5.28e-2
     decode attention      one query x d              2e-2     8.22e-3   (with a bf16 P, as the flash kernels)
     layer / rms / embed   one row                    1e-2     2.25e-3
@@ -60,6 +61,12 @@ against fp64 (COS_ATOL) for fp32 and bf16 tables alike; the same formula in fp32
 on every case.  The sampler, cosine_topk's order and the byte-moving glue kernels are exact.
 
 Nothing here is calibrated against what the HIP kernels return.
+
+Which kernel a case runs is asserted, not assumed: the GEMM cases force a tile and read
+``gemm_last_plan()``, the attention cases name the instantiation launch_attention must pick
+under default knobs and read ``attention_last_kernel()`` (ATTN_ROUNDUP_D, PREFILL_CASE,
+ATTN_WIDE_CASES).  The raster cases (RASTER_GROUPS) walk an 18-tile grid under every group size:
+a tile the mapping misses stays NaN in the guarded output.
 
 Two things the kernels' own rules set.  Causal attention has no key that every query must
 ignore (key q + 1 is masked for query q and valid for the queries after it), so the causal
@@ -256,6 +263,55 @@ def gemm_inputs(c: GemmCase):
     s = 1000 + 7 * c.M + 3 * c.N + c.K
     return (rnd(c.M, c.K, seed=s), rnd(Nw, c.K, scale=c.K ** -0.5, seed=s + 1), rnd(Nw, scale=0.1, seed=s + 2),
             rnd(c.M, c.N, seed=s + 3))
+
+
+# ---- the tile raster (gemm_impl.h tile_of after common.h xcd_remap; gemm_set_raster).  G: M tiles
+# per raster group; 0 is the compiled default (4), 1 the plain row-major walk, 8 more than nM.
+# nM = 6 gives G = 4 and 5 a partial last group (nM > G, nM % G != 0), G = 3 two whole groups
+RASTER_GROUPS = (0, 1, 3, 4, 5, 8)
+RASTER_TILES = (6, 3)        # nM x nN = 18 tiles: no multiple of the 8 XCDs (xcd_remap's tail) nor of any G > 1
+RASTER_CONV = (1, 23, 28, 64, 264, 1)      # B, H, W, Cin, Cout, stride at tile 0: M = 644 = 5 * 128 + 4, N = 2 * 128 + 8
+
+
+def raster_gemm_cases(menu) -> list:
+    """one live row of each family, one with producer waves, and the gated instantiation of one
+    static and one ping-pong row (the first of each in the menu), at M = 5 BM + 1 and N = 2 BN + 8
+    (a gated block covers BN / 2 outputs: N = BN + 8) with K = one k-tile (gemm_cases' rule)"""
+    def first(pred):
+        return next(r for r in menu if pred(r))
+    rows = [(first(lambda r, f=f: r[1] == f), False) for f in ("static", "pingpong", "deep")]
+    rows.append((first(lambda r: r[1] != "areg" and r[6] > 0), False))
+    rows += [(first(lambda r, f=f: r[1] == f and r[7]), True) for f in ("static", "pingpong")]
+    cases = []
+    for (cid, fam, BM, BN, *_), gated in rows:
+        assert BN > 16
+        cases.append(GemmCase(cid, 1, 5 * BM + 1, BN + 8 if gated else 2 * BN + 8, 72 if fam == "static" else 64,
+                              "geglu" if gated else "silu"))
+    return cases
+
+
+def raster_tiles(c: GemmCase, menu) -> tuple:
+    """(nM, nN) of a forced case"""
+    _, _, BM, BN, *_ = next(r for r in menu if r[0] == c.cfg)
+    return -(-c.M // BM), -(-c.N // (BN // 2 if c.act == "geglu" else BN))
+
+
+def tile_of_model(lin, nM, nN, G):
+    """gemm_impl.h tile_of for G >= 1 on the CPU: (tm, tn) of linear index ``lin``"""
+    G = min(G, nM)
+    if G <= 1:
+        return lin // nN, lin % nN
+    grp = lin // (G * nN)
+    gs = min(G, nM - grp * G)
+    r = lin - grp * G * nN
+    return grp * G + r % gs, r // gs
+
+
+def xcd_remap_model(bid, n):
+    """common.h xcd_remap: block ``bid`` of ``n`` round-robin over 8 XCDs -> a contiguous range per XCD"""
+    q, r = divmod(n, 8)
+    xcd, idx = bid % 8, bid // 8
+    return (xcd * (q + 1) if xcd < r else r * (q + 1) + (xcd - r) * q) + idx
 
 
 def linear64(x, w, b=None, r=None, act=None):
@@ -490,6 +546,45 @@ def attn_cases(d, H=2, Hk=None):
 
 
 GQA_CASE = AttnCase(3, 65, 65, 4, 2, 64, None, True)
+
+# ---- every instantiation launch_attention can pick (attention.hip), by what attention_last_kernel()
+# reports: (family, DQK, DO, waves per block).  A head dim below each template width (the round-up
+# branch, d < DQK) and the two exact widths without an edge test of their own
+ATTN_ROUNDUP_D = (24, 48, 88, 96, 112, 128, 136)
+ATTN_TEMPLATE_WIDTHS = (32, 64, 96, 128, 160)
+LM_HEADS = (8, 2)            # (H, Hk) of the GQA cases at the LM's head dim 128
+# LM prefill: causal over five key tiles in 4-wave blocks, GQA, K/V a strided (KV-cache) view
+PREFILL_CASE = AttnCase(3, 257, 257, 8, 2, 128, None, True)
+PREFILL_KERNEL = ("fwd", 128, 128, 4)
+
+
+def attn_template_width(d) -> int:
+    """the template a head dim that has no kernel of its own rounds up to"""
+    return next(w for w in ATTN_TEMPLATE_WIDTHS if d <= w)
+
+
+def cyc(B, Nk) -> tuple:
+    """kv_lens (Nk, 1, 0) taking turns; B = 3n keeps the last batch without a key"""
+    return tuple((Nk, 1, 0)[b % 3] for b in range(B))
+
+
+# The smallest grids that cross the wave-count thresholds under default knobs: 1024 blocks of 256
+# queries (8 waves, DO <= 96), 256 such blocks for the 16x16 d = 40 kernel, 512 blocks of 128 queries
+# (4 waves at Nq < 256).  Nq = 257: the second 8-wave block has seven idle waves that still take
+# every barrier and staging load.  (case, the kernel it must launch, the kernel under the d = 40
+# variant "32x32" where that differs)
+ATTN_WIDE_CASES = [
+    (AttnCase(33, 257, 129, 16, 16, 32, cyc(33, 129), False), ("fwd", 32, 32, 8), None),
+    (AttnCase(33, 257, 257, 16, 4, 64, None, True), ("fwd", 64, 64, 8), None),              # GQA, causal
+    (AttnCase(33, 257, 129, 16, 16, 80, cyc(33, 129), False), ("fwd", 80, 96, 8), None),    # the ones column
+    (AttnCase(33, 257, 257, 16, 16, 96, None, True), ("fwd", 96, 96, 8), None),
+    (AttnCase(33, 257, 257, 16, 16, 40, None, True), ("fwd", 48, 64, 8), None),             # the MF path
+    (AttnCase(3, 257, 257, 2, 2, 40, None, True), ("fwd", 48, 64, 4), None),
+    (AttnCase(33, 257, 129, 4, 4, 40, cyc(33, 129), False), ("a16", 48, 48, 8), ("fwd", 48, 64, 4)),
+    (AttnCase(66, 33, 65, 8, 8, 64, cyc(66, 65), False), ("fwd", 64, 64, 4), None),         # blocks4 >= 512: three idle waves
+]
+ATTN_KNOBS = ("CASSMANTLE_ATTN_NW", "CASSMANTLE_ATTN_NW4_MIN", "CASSMANTLE_ATTN16", "CASSMANTLE_ATTN16_NW8_MIN")
+
 D512_SPLIT_CASE = AttnCase(3, 33, 300, 2, 2, 512, (300, 1, 0), False)     # 6 blocks, 300 keys: two key splits (d512_splits)
 
 

@@ -5,6 +5,8 @@ same bf16 inputs (:func:`kernel_oracle.block_rel_err`) under the family's existi
 tolerance.  Shapes: one full tile, one partial tile and a tail.  The attention data makes the edge
 keys matter (kernel_oracle.attn_data).  test_kernel_oracle.py shows, without a GPU, that these
 checks reject the bugs the whole-tensor error lets through and accept the ideal kernel."""
+import os
+
 import pytest
 import torch
 
@@ -182,6 +184,53 @@ def test_row_stats_producer_and_consumer_edges():
     ko.check_guards(rs)
 
 
+# ------------------------------------------------------------------------------ the tile raster
+@pytest.fixture
+def raster(force_cfg):
+    """gemm_set_raster for plain and gated calls alike; the compiled default and no override afterwards"""
+    assert "CASSMANTLE_GEMM_RASTER" not in os.environ, "CASSMANTLE_GEMM_RASTER must be unset: the G = 0 case is the compiled default"
+    yield lambda G: ext().gemm_set_raster(G, G)
+    ext().gemm_set_raster(0, 0)
+
+
+@pytest.mark.parametrize("c", ko.raster_gemm_cases(MENU), ids=lambda c: c.id)
+def test_gemm_raster_edges(c, force_cfg, raster):
+    """6 x 3 tiles under every raster group: a tile the mapping misses stays NaN in the guarded
+    output, one it maps outside the grid writes nothing or the guards"""
+    assert ko.raster_tiles(c, MENU) == ko.RASTER_TILES
+    x, w, b, r = ko.gemm_inputs(c)
+    y64 = ko.linear64(x, w, b, r, c.act)
+    xp, wp, bp, rp = P(x), P(w), P(b), P(r)
+    errs = []
+    for G_ in ko.RASTER_GROUPS:
+        g = G((c.M, c.N))
+        raster(G_)
+        force_cfg(c.cfg, c.split)
+        ops.linear(xp, wp, bp, residual=rp, act=c.act, out=g.view)
+        assert last_plan() == (c.cfg, c.split)
+        check(g, y64, "gemm", f"raster G={G_} {c.id}", errs=errs)
+    assert errs == []
+
+
+def test_conv_raster_edges(force_cfg, raster):
+    B, H, W, Cin, Cout, stride = ko.RASTER_CONV
+    assert (-(-B * H * W // TILE[0][2]), -(-Cout // TILE[0][3])) == ko.RASTER_TILES
+    x, w, b, cb, res = ko.conv_inputs(B, H, W, Cin, Cout, stride)
+    y64 = ko.conv64(x, w, b, cb, res, stride).flatten(0, 2)
+    xp, wp, bp, rp, cbp = P(x), P(w), P(b), P(res), P(cb)
+    errs = []
+    for G_ in ko.RASTER_GROUPS:
+        g, st = G((B, H, W, Cout)), zeroed_stats(B, Cout, 2)
+        raster(G_)
+        force_cfg(0, 1)
+        ops.conv2d(xp, wp, bp, stride=stride, padding=1, residual=rp, chan_bias=cbp, stats=st.view, out=g.view)
+        assert last_plan() == (0, 1)
+        check(g, y64, "conv", f"raster G={G_} {B}x{H}x{W} {Cin}->{Cout}", errs=errs)
+        ko.check_guards(st)
+        check_stats(st.view, g.view, B)
+    assert errs == []
+
+
 # ------------------------------------------------------------------------------ conv
 @pytest.mark.parametrize("B,H,W,Cin,Cout,stride", ko.CONV_CASES)
 def test_conv_edges(B, H, W, Cin, Cout, stride):
@@ -217,9 +266,14 @@ def test_conv_up2_edges(Cin, forced, force_cfg):
 
 
 # ------------------------------------------------------------------------------ attention
-def run_attention(c, errs, family="attention", fp8=False, prepack=False, what=""):
+def attn_reference(c):
+    """q, k, v and the fp64 reference of a case (for a case that runs under more than one kernel)"""
     q, k, v = ko.attn_data(c)
-    o64 = ko.attention64(q, k, v, c.lens, c.causal)
+    return q, k, v, ko.attention64(q, k, v, c.lens, c.causal)
+
+
+def run_attention(c, errs, family="attention", fp8=False, prepack=False, what="", data=None):
+    q, k, v, o64 = attn_reference(c) if data is None else data
     qp, kp, vp = (P(t, strided=True, row_dims=2) for t in (q, k, v))
     assert (c.Nq == 1 or qp.stride(1) > c.H * c.d) and (c.Nk == 1 or kp.stride(1) > c.Hk * c.d)
     lens = None if c.lens is None else torch.tensor(c.lens, dtype=torch.int32, device=DEV)
@@ -266,6 +320,76 @@ def test_attention_d512_edges():
 def test_attention_gqa_causal_edges():
     errs = []
     run_attention(ko.GQA_CASE, errs)
+    assert errs == []
+
+
+def last_kernel():
+    return tuple(ext().attention_last_kernel())
+
+
+@pytest.fixture
+def default_attention_dispatch():
+    """the kernels the cases below name are the ones launch_attention picks with its A/B knobs unset"""
+    for var in ko.ATTN_KNOBS:
+        assert var not in os.environ, f"{var} must be unset: it changes which attention kernel a shape launches"
+
+
+def test_attention_last_kernel_follows_every_launcher(default_attention_dispatch):
+    """the record is overwritten by the fp8 and d = 512 launchers too, so it is never another call's"""
+    errs = []
+    c = ko.attn_cases(64)[6]
+    run_attention(c, errs)
+    assert last_kernel()[:3] == ("fwd", 64, 64)
+    run_attention(c, errs, "fp8", fp8=True)
+    assert last_kernel()[:3] == ("fp8", 64, 64) and last_kernel()[3] in (4, 8)
+    run_attention(ko.attn_cases(512)[6], errs)
+    assert last_kernel() == ("d512", 512, 512, 8)
+    run_attention(ko.attn_cases(40)[6], errs)
+    assert last_kernel()[0] == "a16"
+    assert errs == []
+
+
+@pytest.mark.parametrize("d", ko.ATTN_ROUNDUP_D)
+def test_attention_roundup_edges(d, default_attention_dispatch):
+    """a head dim below each template width (zero-filled columns in LDS, stores cut at d), and
+    the 96- and 128-wide templates at their own width"""
+    w = ko.attn_template_width(d)
+    errs = []
+    for c in ko.attn_cases(d):
+        run_attention(c, errs)
+        assert last_kernel()[:3] == ("fwd", w, w), (c.id, last_kernel())
+    assert errs == []
+
+
+def test_attention_lm_prefill_edges(default_attention_dispatch):
+    """models/lm.py's prefill call: d = 128, four query heads per K/V head, lens or causal, Q/K/V
+    strided views as the KV cache's; then causal over five key tiles in 4-wave blocks"""
+    errs, waves = [], set()
+    for c in ko.attn_cases(128, *ko.LM_HEADS):
+        run_attention(c, errs)
+        assert last_kernel()[:3] == ("fwd", 128, 128), (c.id, last_kernel())
+        waves.add(last_kernel()[3])
+    assert waves == {2, 4}
+    run_attention(ko.PREFILL_CASE, errs, what="prefill ")
+    assert last_kernel() == ko.PREFILL_KERNEL
+    assert errs == []
+
+
+@pytest.mark.parametrize("c,kernel,kernel_32x32", ko.ATTN_WIDE_CASES, ids=[c.id for c, _, _ in ko.ATTN_WIDE_CASES])
+def test_attention_wide_grid_edges(c, kernel, kernel_32x32, default_attention_dispatch):
+    """the grids that reach the 8-wave blocks, the 8-wave 16x16 d = 40 kernel and the 512-block
+    rule; the d = 40 row also under the 32x32 variant, on the same data"""
+    errs, data = [], attn_reference(c)
+    run_attention(c, errs, what=f"B={c.B} ", data=data)
+    assert last_kernel() == kernel, (c.id, last_kernel())
+    if kernel_32x32 is not None:
+        try:
+            for variant, want in (("16x16", kernel), ("32x32", kernel_32x32)):
+                ops.set_attention_d40_variant(variant)
+                run_attention(c, errs, what=f"{variant} B={c.B} ", data=data)
+                assert last_kernel() == want, (c.id, variant, last_kernel())
+        finally:
+            ops.set_attention_d40_variant(None)
     assert errs == []
 
 

@@ -39,7 +39,7 @@ def global_rel_err(out, ref64):
 
 # ------------------------------------------------------------------------------ the ideal kernel passes
 def test_ideal_gemm():
-    for c in ko.gemm_cases(header_rows()):
+    for c in ko.gemm_cases(header_rows()) + ko.raster_gemm_cases(header_rows()):
         x, w, b, r = ko.gemm_inputs(c)
         y64 = ko.linear64(x, w, b, r, c.act)
         floor("gemm", block_rel_err(bf16_round(y64), y64), c.id)
@@ -66,7 +66,7 @@ def test_ideal_gemm():
 
 
 def test_ideal_conv():
-    for B, H, W, Cin, Cout, stride in ko.CONV_CASES:
+    for B, H, W, Cin, Cout, stride in ko.CONV_CASES + [ko.RASTER_CONV]:
         args = ko.conv_inputs(B, H, W, Cin, Cout, stride)
         y64 = ko.conv64(*args, stride=stride).flatten(0, 2)
         floor("conv", block_rel_err(bf16_round(y64), y64), (B, H, W, Cin, Cout, stride))
@@ -94,14 +94,26 @@ def test_conv_model_is_the_reference():
         assert (y != bf16_round(y64)).float().mean().item() < 1e-3, c.id       # (a summation order apart)
 
 
-@pytest.mark.parametrize("d", [32, 40, 64, 80, 160, 256, 512])
+IDEAL_ATTN = ([(str(d), d) for d in (32, 40, 64, 80, 160, 256, 512) + ko.ATTN_ROUNDUP_D] +
+              [("lm", "lm")] + [("wide-" + c.id, c) for c, _, _ in ko.ATTN_WIDE_CASES])
+
+
+@pytest.mark.parametrize("d", [d for _, d in IDEAL_ATTN], ids=[i for i, _ in IDEAL_ATTN])
 def test_ideal_attention(d):
-    cases = ko.attn_cases(d) + ([ko.GQA_CASE] if d == 64 else []) + ([ko.D512_SPLIT_CASE] if d == 512 else [])
+    """``d``: a head dim (attn_cases and the single cases at that dim), "lm" (the GQA and prefill
+    cases at d = 128) or one wide-grid case"""
+    if isinstance(d, ko.AttnCase):
+        cases = [d]
+    elif d == "lm":
+        cases = ko.attn_cases(128, *ko.LM_HEADS) + [ko.PREFILL_CASE]
+    else:
+        cases = ko.attn_cases(d) + ([ko.GQA_CASE] if d == 64 else []) + ([ko.D512_SPLIT_CASE] if d == 512 else [])
+    row = None if d in (32, 40, 64, 80, 160, 256, 512) else "attention, dispatch"     # a table line for the instantiation cases
     for c in cases:
         q, k, v = ko.attn_data(c)
         o64 = ko.attention64(q, k, v, c.lens, c.causal)
-        floor("attention", block_rel_err(ko.ideal_attention(q, k, v, c.lens, c.causal), o64, (1, 16, 1, None)), c.id)
-        if d == 64:
+        floor("attention", block_rel_err(ko.ideal_attention(q, k, v, c.lens, c.causal), o64, (1, 16, 1, None)), c.id, row)
+        if d == 64:                                           # the cases the fp8 kernel runs
             floor("fp8", block_rel_err(ko.ideal_attention(q, k, v, c.lens, c.causal, fp8=True), o64, (1, 16, 1, None)), c.id)
 
 
@@ -196,6 +208,78 @@ def test_causal_future_key_included_fails():
     q, k, v = ko.attn_data(c)
     o64 = ko.attention64(q, k, v, None, True)
     assert block_rel_err(ko.ideal_attention(q, k, v, None, True, extra_key=True), o64, (1, 16, 1, None)) > BOUND["attention"]
+
+
+def test_planted_key_bugs_fail_on_a_wide_grid():
+    """B = 33, H = 16 (the 8-wave d = 32 case): one block in 2112 still decides"""
+    c = ko.ATTN_WIDE_CASES[0][0]
+    assert c.B == 33 and c.lens is not None
+    q, k, v = ko.attn_data(c)
+    o64 = ko.attention64(q, k, v, c.lens)
+    for bug in ({"drop_last": True}, {"extra_key": True}):
+        e = block_rel_err(ko.ideal_attention(q, k, v, c.lens, **bug), o64, (1, 16, 1, None))
+        print(f"wide grid {bug}: worst block {e:.3e}")
+        assert e > BOUND["attention"], bug
+
+
+def test_wide_cases_cross_the_launch_thresholds():
+    """the grid arithmetic of launch_nw / launch_attention (attention.hip) on the wide cases: each
+    sits at or just above the block count that selects the kernel it names, at the smallest B"""
+    for c, want, alt in ko.ATTN_WIDE_CASES:
+        blocks4, blocks8 = -(-c.Nq // 128) * c.H * c.B, -(-c.Nq // 256) * c.H * c.B
+        for fam, dqk, do, nw in (want,) + ((alt,) if alt else ()):
+            if fam == "a16":
+                assert nw == 8 and not c.causal and c.d == 40 and blocks8 >= 256 > -(-c.Nq // 256) * c.H * (c.B - 3)
+            elif nw == 8:
+                assert do <= 96 and blocks8 >= 1024 > -(-c.Nq // 256) * c.H * (c.B - 3), c.id
+            else:
+                assert nw == 4 and (do > 96 or blocks8 < 1024) and (blocks4 >= 512 or (c.Nq >= 256 and blocks4 >= 16)), c.id
+        assert c.lens is None or (len(c.lens) == c.B and c.lens[-1] == 0)
+    c = ko.PREFILL_CASE
+    assert ko.PREFILL_KERNEL[2] > 96 and c.Nq >= 256 and -(-c.Nq // 128) * c.H * c.B >= 16 and -(-c.Nk // 64) == 5
+    assert {ko.attn_template_width(d) for d in ko.ATTN_ROUNDUP_D} == set(ko.ATTN_TEMPLATE_WIDTHS)
+    assert {d for d in ko.ATTN_ROUNDUP_D if d in ko.ATTN_TEMPLATE_WIDTHS} == {96, 128}
+
+
+def _raster_walk(nM, nN, G, partial_group=True):
+    """tiles in launch order: every block id through xcd_remap, then tile_of.  ``partial_group=False``:
+    the planted raster whose last group is as tall as the others"""
+    tiles = []
+    for bid in range(nM * nN):
+        lin = ko.xcd_remap_model(bid, nM * nN)
+        if partial_group or G <= 1:
+            tiles.append(ko.tile_of_model(lin, nM, nN, G))
+        else:
+            g = min(G, nM)
+            grp, r = divmod(lin, g * nN)
+            tiles.append((grp * g + r % g, r // g))
+    return tiles
+
+
+def test_raster_is_a_bijection_and_a_planted_one_fails():
+    """the CPU transcript of xcd_remap and tile_of visits each of the 18 tiles once for every G;
+    without the partial last group, a tile is never written and another is outside the grid: the
+    NaN-prefilled guarded output shows it as an infinite block"""
+    nM, nN = ko.RASTER_TILES
+    for c in ko.raster_gemm_cases(header_rows()):
+        assert ko.raster_tiles(c, header_rows()) == (nM, nN), c.id
+    all_tiles = sorted((m, n) for m in range(nM) for n in range(nN))
+    partial = []
+    for G in ko.RASTER_GROUPS:
+        g = G or 4
+        assert sorted(_raster_walk(nM, nN, g)) == all_tiles, G
+        if nM > g > 1 and nM % g:
+            partial.append(G)
+            bad = _raster_walk(nM, nN, g, partial_group=False)
+            assert sorted(bad) != all_tiles
+            c = ko.GemmCase(3, 1, 5 * 128 + 1, 2 * 64 + 8, 72, "silu")
+            y64 = ko.linear64(*ko.gemm_inputs(c), c.act)
+            out = ko.guarded((c.M, c.N))
+            for tm, tn in bad:
+                if tm < nM:
+                    out.view[tm * 128:(tm + 1) * 128, tn * 64:(tn + 1) * 64] = bf16_round(y64)[tm * 128:(tm + 1) * 128, tn * 64:(tn + 1) * 64]
+            assert block_rel_err(out.view, y64) == math.inf
+    assert partial == [0, 4, 5]
 
 
 def test_decode_key_past_lens_or_dropped_fails():
