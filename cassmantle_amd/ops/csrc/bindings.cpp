@@ -83,6 +83,7 @@ void run_gemm(GemmArgs& p, const at::Tensor& like) {
   if (p.kv8 != nullptr) p.split = 1;
   long long* post_stats = nullptr;
   if (p.stats != nullptr && (p.out_f32 || p.M <= 8 || (p.batch != 1 && !p.parity) || p.act == 4 || p.act == 6)) {
+    TORCH_CHECK(p.N <= GN_MAX_C, "gemm stats: the separate statistics pass takes N <= ", GN_MAX_C);
     post_stats = p.stats;
     p.stats = nullptr;
   }
@@ -393,6 +394,9 @@ void group_norm(const at::Tensor& x, const at::Tensor& gamma, const at::Tensor& 
   const int C = (int)x.size(-1);
   const long long S = x.numel() / ((long long)B * C);
   TORCH_CHECK(C % 8 == 0 && C % groups == 0, "group_norm: C must be a multiple of 8 and of groups");
+  // the statistics and apply kernels exist for 1 and 2 vectors per thread (C <= 4096); past that a
+  // thread would skip its third vector and the statistics kernel's LDS request passes 64 KiB
+  TORCH_CHECK(C <= GN_MAX_C, "group_norm: C <= ", GN_MAX_C);
   auto ws = at::empty({group_norm_workspace(B, S, C)}, x.options().dtype(at::kFloat));
   launch_group_norm(bptr(x), bptr(gamma), bptr(beta), bptr_mut(out), ws.data_ptr<float>(), B, S, C, (int)groups,
                     (float)eps, (int)silu, cur_stream());
@@ -450,7 +454,7 @@ void channel_stats(const at::Tensor& x, at::Tensor& stats) {
   const int B = (int)x.size(0);
   const int C = (int)x.size(-1);
   const long long S = x.numel() / ((long long)B * C);
-  TORCH_CHECK(C % 8 == 0, "channel_stats: C % 8 == 0");
+  TORCH_CHECK(C % 8 == 0 && C <= GN_MAX_C, "channel_stats: C % 8 == 0 and C <= ", GN_MAX_C);
   launch_channel_stats(bptr(x), opt_stats(stats, B, C), B, S, C, cur_stream());
 }
 
@@ -1308,6 +1312,18 @@ PYBIND11_MODULE(_C, m) {
   m.def("conv2d_up2", &conv2d_up2, nogil());
   m.def("bmm_nt", &bmm_nt, nogil());
   m.def("group_norm", &group_norm, nogil());
+  // the launch geometry the GroupNorm launchers use for x [B, S, C] (norm.hip group_norm_geometry)
+  m.def("group_norm_geometry", [](int64_t B, int64_t S, int64_t C) {
+    TORCH_CHECK(B > 0 && S > 0 && C > 0 && C % 8 == 0, "group_norm_geometry: B, S > 0 and C % 8 == 0");
+    const GnLaunchGeom g = group_norm_geometry((int)B, (long long)S, (int)C);
+    py::dict two, fed, out;
+    two["VPT"] = g.vpt; two["T"] = g.T; two["R"] = g.R; two["chunks"] = g.chunks;
+    two["rows_per_chunk"] = g.rpc; two["rows_per_block"] = g.apply_rpb; two["blocks"] = g.apply_nb;
+    fed["VPT"] = g.cs_vpt; fed["T"] = g.cs_T; fed["R"] = g.cs_R; fed["U"] = g.cs_U;
+    fed["rows_per_block"] = g.cs_rpb; fed["blocks"] = g.cs_nb;
+    out["two_pass"] = two; out["stats_fed"] = fed;
+    return out;
+  });
   m.def("layer_norm", &layer_norm, nogil());
   m.def("embed_layer_norm", &embed_layer_norm, nogil());
   m.def("group_norm_stats", &group_norm_stats, nogil());

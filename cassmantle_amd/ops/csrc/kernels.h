@@ -136,6 +136,21 @@ void launch_group_norm_cs(const uint16_t* x, const uint16_t* x2, const long long
 // without a fused path)
 void launch_channel_stats(const uint16_t* x, long long* stats, int B, long long S, int C, hipStream_t s);
 long long group_norm_workspace(int B, long long S, int C);
+// The launch geometry of the three launchers above for x [B][S][C], computed in one place (as
+// gemm_plan for the GEMMs) so tests can assert which branches of the kernels a shape reaches.
+// Two-pass path (launch_group_norm, launch_channel_stats): VPT 8-channel vectors per thread,
+// T vector lanes x R row lanes, statistics chunks of rpc rows, apply blocks of apply_rpb rows.
+// Statistics-fed path (launch_group_norm_cs): its own VPT / T / R, U rows per thread in flight,
+// blocks of cs_rpb rows.  launch_group_norm and launch_channel_stats instantiate VPT 1 and 2
+// only (C <= GN_MAX_C); launch_group_norm_cs also VPT 4.
+constexpr int GN_MAX_C = 4096;
+struct GnLaunchGeom {
+  int vpt, T, R, chunks;
+  long long rpc, apply_rpb, apply_nb;
+  int cs_vpt, cs_T, cs_R, cs_U;
+  long long cs_rpb, cs_nb;
+};
+GnLaunchGeom group_norm_geometry(int B, long long S, int C);
 void launch_layer_norm(const uint16_t* x, const uint16_t* gamma, const uint16_t* beta, uint16_t* y,
                        long long rows, int D, float eps, hipStream_t s);
 // per-row (mean, rstd) float2 of [rows][D] (LayerNorm statistics for a folded-LN GEMM)

@@ -522,39 +522,29 @@ int gn_chunks(int B, long long S, int R) {
 }  // namespace
 
 long long group_norm_workspace(int B, long long S, int C) {
-  const GnGeom g = gn_geom(C);
-  const int chunks = gn_chunks(B, S, g.R);
+  const int chunks = group_norm_geometry(B, S, C).chunks;
   return (long long)B * chunks * 2 * C + 2LL * B * C;   // floats (>= partials + stats for any G)
 }
 
 void launch_group_norm(const uint16_t* x, const uint16_t* gamma, const uint16_t* beta, uint16_t* y,
                        float* ws, int B, long long S, int C, int G, float eps, int silu, hipStream_t s) {
-  const GnGeom g = gn_geom(C);
-  const int chunks = gn_chunks(B, S, g.R);
-  const long long rpc = (S + chunks - 1) / chunks;
+  const GnLaunchGeom g = group_norm_geometry(B, S, C);     // (the binding refuses C > GN_MAX_C: VPT 1 and 2 only)
   float* part = ws;
-  float* stats = ws + (long long)B * chunks * G * 2;
+  float* stats = ws + (long long)B * g.chunks * G * 2;
   const size_t shs = sizeof(float) * (2LL * g.R * C + 2LL * C);
-  if (g.VPT == 1)
-    hipLaunchKernelGGL(gn_stats_kernel<1>, dim3(chunks, B), dim3(GN_THREADS), shs, s, x, part, S, C, G, g.T, g.R,
-                       chunks, rpc);
+  if (g.vpt == 1)
+    hipLaunchKernelGGL(gn_stats_kernel<1>, dim3(g.chunks, B), dim3(GN_THREADS), shs, s, x, part, S, C, G, g.T, g.R,
+                       g.chunks, g.rpc);
   else
-    hipLaunchKernelGGL(gn_stats_kernel<2>, dim3(chunks, B), dim3(GN_THREADS), shs, s, x, part, S, C, G, g.T, g.R,
-                       chunks, rpc);
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(G, B), dim3(64), 0, s, part, stats, S, C, G, chunks, eps);
-  // apply: ~8 rows per row-lane per block
-  long long rpb = 2LL * GN_UNROLL * g.R;                   // whole GN_UNROLL-row iterations per thread
-  long long nb = (S + rpb - 1) / rpb;
-  if (nb * B < 2048) {                                     // small images: shorter blocks, more of them
-    rpb = (long long)GN_UNROLL * g.R;
-    nb = (S + rpb - 1) / rpb;
-  }
-  if (g.VPT == 1)
-    hipLaunchKernelGGL(gn_apply_kernel<1>, dim3((unsigned)nb, B), dim3(GN_THREADS), 0, s, x, stats, gamma, beta, y, S,
-                       C, G, g.T, g.R, rpb, silu);
+    hipLaunchKernelGGL(gn_stats_kernel<2>, dim3(g.chunks, B), dim3(GN_THREADS), shs, s, x, part, S, C, G, g.T, g.R,
+                       g.chunks, g.rpc);
+  hipLaunchKernelGGL(gn_finalize_kernel, dim3(G, B), dim3(64), 0, s, part, stats, S, C, G, g.chunks, eps);
+  if (g.vpt == 1)
+    hipLaunchKernelGGL(gn_apply_kernel<1>, dim3((unsigned)g.apply_nb, B), dim3(GN_THREADS), 0, s, x, stats, gamma, beta,
+                       y, S, C, G, g.T, g.R, g.apply_rpb, silu);
   else
-    hipLaunchKernelGGL(gn_apply_kernel<2>, dim3((unsigned)nb, B), dim3(GN_THREADS), 0, s, x, stats, gamma, beta, y, S,
-                       C, G, g.T, g.R, rpb, silu);
+    hipLaunchKernelGGL(gn_apply_kernel<2>, dim3((unsigned)g.apply_nb, B), dim3(GN_THREADS), 0, s, x, stats, gamma, beta,
+                       y, S, C, G, g.T, g.R, g.apply_rpb, silu);
 }
 
 // Apply geometry: 8-channel vectors per thread (VPT in {1, 2}) chosen for the most active threads
@@ -598,11 +588,29 @@ static GnGeom gn_apply_geom(int C) {
   return g;
 }
 
-template <int VPT, int U>
-static void launch_apply(const uint16_t* x, const uint16_t* x2, const long long* stats_a, int Ca, const long long* stats_b,
-                         const uint16_t* gamma, const uint16_t* beta, uint16_t* y, int B, long long S, int C, int G,
-                         float eps, int silu, const GnGeom& g, hipStream_t s) {
-  const long long step = (long long)U * g.R;                       // rows per block iteration
+// every launch parameter of the GroupNorm kernels that depends on (B, S, C), for the launchers
+// below and for ext().group_norm_geometry (tests/kernel_oracle.py gn_geometry_model is its transcript)
+GnLaunchGeom group_norm_geometry(int B, long long S, int C) {
+  GnLaunchGeom o;
+  // ---- two-pass path: statistics chunks, then ~8 rows per row-lane per apply block
+  const GnGeom g = gn_geom(C);
+  o.vpt = g.VPT; o.T = g.T; o.R = g.R;
+  o.chunks = gn_chunks(B, S, g.R);
+  o.rpc = (S + o.chunks - 1) / o.chunks;
+  o.apply_rpb = 2LL * GN_UNROLL * g.R;                     // whole GN_UNROLL-row iterations per thread
+  o.apply_nb = (S + o.apply_rpb - 1) / o.apply_rpb;
+  if (o.apply_nb * B < 2048) {                             // small images: shorter blocks, more of them
+    o.apply_rpb = (long long)GN_UNROLL * g.R;
+    o.apply_nb = (S + o.apply_rpb - 1) / o.apply_rpb;
+  }
+  // ---- statistics-fed path: U rows per thread, at most 16 vector loads (VPT x U) in flight per thread
+  const GnGeom a = gn_apply_geom(C);
+  o.cs_vpt = a.VPT; o.cs_T = a.T; o.cs_R = a.R;
+  constexpr int U = GN_APPLY_U;
+  constexpr int U2 = U * 2 > 16 ? 8 : U, U4 = U * 4 > 16 ? 4 : U;
+  if (GN_U8_RULE && C >= 512 && C <= 1024 && S >= 4096) o.cs_U = 8;
+  else o.cs_U = a.VPT == 1 ? U : (a.VPT == 2 ? U2 : U4);
+  const long long step = (long long)o.cs_U * a.R;                  // rows per block iteration
   long long rpb;
   if (GN_APPLY_GEOM) {
     // tensors of >= CASSMANTLE_GN_BIG_MB MiB may take CASSMANTLE_GN_BIG_BLOCKS blocks (A/B knob)
@@ -618,43 +626,49 @@ static void launch_apply(const uint16_t* x, const uint16_t* x2, const long long*
     if (want < (32LL << 10) / (2LL * C)) want = (32LL << 10) / (2LL * C);
     rpb = step * ((want + step - 1) / step);
     while (rpb > step && ((S + rpb - 1) / rpb) * B < 1024) rpb -= step;
-    if (rpb == step && ((S + rpb - 1) / rpb) * B < 256) rpb = step / 2 >= g.R ? step / 2 : g.R;
+    if (rpb == step && ((S + rpb - 1) / rpb) * B < 256) rpb = step / 2 >= a.R ? step / 2 : a.R;
   }
-  const long long nb = (S + rpb - 1) / rpb;
+  o.cs_rpb = rpb;
+  o.cs_nb = (S + rpb - 1) / rpb;
+  return o;
+}
+
+template <int VPT, int U>
+static void launch_apply(const uint16_t* x, const uint16_t* x2, const long long* stats_a, int Ca, const long long* stats_b,
+                         const uint16_t* gamma, const uint16_t* beta, uint16_t* y, int B, long long S, int C, int G,
+                         float eps, int silu, const GnLaunchGeom& g, hipStream_t s) {
   const size_t shs = sizeof(float) * 2 * G;
-  hipLaunchKernelGGL((gn_apply_cs_kernel<VPT, U>), dim3((unsigned)nb, B), dim3(GN_THREADS), shs, s, x, x2, stats_a, Ca,
-                     stats_b, gamma, beta, y, S, C, G, g.T, g.R, rpb, eps, silu);
+  hipLaunchKernelGGL((gn_apply_cs_kernel<VPT, U>), dim3((unsigned)g.cs_nb, B), dim3(GN_THREADS), shs, s, x, x2, stats_a, Ca,
+                     stats_b, gamma, beta, y, S, C, G, g.cs_T, g.cs_R, g.cs_rpb, eps, silu);
 }
 
 void launch_group_norm_cs(const uint16_t* x, const uint16_t* x2, const long long* stats_a, int Ca, const long long* stats_b,
                           const uint16_t* gamma, const uint16_t* beta, uint16_t* y, int B, long long S, int C,
                           int G, float eps, int silu, hipStream_t s) {
-  const GnGeom g = gn_apply_geom(C);
+  const GnLaunchGeom g = group_norm_geometry(B, S, C);
   if (stats_b == nullptr) Ca = C;
-  // U rows per thread, at most 16 vector loads (VPT x U) in flight per thread
   constexpr int U = GN_APPLY_U;
   constexpr int U2 = U * 2 > 16 ? 8 : U, U4 = U * 4 > 16 ? 4 : U;
-  if (GN_U8_RULE && C >= 512 && C <= 1024 && S >= 4096) {
-    if (g.VPT == 1) launch_apply<1, 8>(x, x2, stats_a, Ca, stats_b, gamma, beta, y, B, S, C, G, eps, silu, g, s);
+  if (g.cs_U == 8 && g.cs_vpt <= 2) {
+    if (g.cs_vpt == 1) launch_apply<1, 8>(x, x2, stats_a, Ca, stats_b, gamma, beta, y, B, S, C, G, eps, silu, g, s);
     else launch_apply<2, 8>(x, x2, stats_a, Ca, stats_b, gamma, beta, y, B, S, C, G, eps, silu, g, s);
     return;
   }
-  if (g.VPT == 1) launch_apply<1, U>(x, x2, stats_a, Ca, stats_b, gamma, beta, y, B, S, C, G, eps, silu, g, s);
-  else if (g.VPT == 2) launch_apply<2, U2>(x, x2, stats_a, Ca, stats_b, gamma, beta, y, B, S, C, G, eps, silu, g, s);
+  if (g.cs_vpt == 1) launch_apply<1, U>(x, x2, stats_a, Ca, stats_b, gamma, beta, y, B, S, C, G, eps, silu, g, s);
+  else if (g.cs_vpt == 2) launch_apply<2, U2>(x, x2, stats_a, Ca, stats_b, gamma, beta, y, B, S, C, G, eps, silu, g, s);
+  // gn_geom's VPT 3 (C > 4096) and 4: T = ceil(V / VPT) lanes, so four vectors per lane cover the row
   else launch_apply<4, U4>(x, x2, stats_a, Ca, stats_b, gamma, beta, y, B, S, C, G, eps, silu, g, s);
 }
 
 void launch_channel_stats(const uint16_t* x, long long* stats, int B, long long S, int C, hipStream_t s) {
-  const GnGeom g = gn_geom(C);
-  const int chunks = gn_chunks(B, S, g.R);
-  const long long rpc = (S + chunks - 1) / chunks;
+  const GnLaunchGeom g = group_norm_geometry(B, S, C);     // (the binding refuses C > GN_MAX_C: VPT 1 and 2 only)
   const size_t shs = sizeof(float) * 2LL * g.R * C;
-  if (g.VPT == 1)
-    hipLaunchKernelGGL(channel_stats_kernel<1>, dim3(chunks, B), dim3(GN_THREADS), shs, s, x, stats, S, C, g.T, g.R,
-                       rpc);
+  if (g.vpt == 1)
+    hipLaunchKernelGGL(channel_stats_kernel<1>, dim3(g.chunks, B), dim3(GN_THREADS), shs, s, x, stats, S, C, g.T, g.R,
+                       g.rpc);
   else
-    hipLaunchKernelGGL(channel_stats_kernel<2>, dim3(chunks, B), dim3(GN_THREADS), shs, s, x, stats, S, C, g.T, g.R,
-                       rpc);
+    hipLaunchKernelGGL(channel_stats_kernel<2>, dim3(g.chunks, B), dim3(GN_THREADS), shs, s, x, stats, S, C, g.T, g.R,
+                       g.rpc);
 }
 
 template <int VPL, bool RMS, bool STATS, bool EMB>

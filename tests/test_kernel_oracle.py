@@ -5,7 +5,12 @@ test_kernel_edges_decode_gpu.py and test_kernel_edges_scorer_gpu.py run, and eac
 the whole-tensor error of tests/test_kernels_gpu.py -- fails its check.  The sampler, the top-k
 and mean_pool_l2 have models of the kernels' own selection rules here; their planted bugs are the
 ones those kernels had or could have (a tie cut one rank too wide, -0.0 keyed below +0.0, a
-padding key that surfaces, the first token of an empty row)."""
+padding key that surfaces, the first token of an empty row).  For norm.hip
+(test_kernel_edges_norm_gpu.py) the launch geometry has a transcript here: every case reaches the
+branches it names, and the planted bugs are those of that geometry (the neighbouring group's or
+image 0's statistics, the last statistics chunk missing, the last vector of an odd row, channels
+past Ca read from the first statistics buffer, a row normalised from the row its load was clamped
+to, two LayerNorm rows reduced together, a row missing from channel_stats)."""
 import math
 
 import pytest
@@ -131,7 +136,8 @@ def test_ideal_decode_attention():
 def test_ideal_norms_and_rope():
     for rows, D in ko.ROW_NORM_CASES:
         x, g, b = ko.norm_inputs(rows, D)
-        for y64 in (ref.layer_norm(x, g, b, 1e-5, dtype=F64), ref.rms_norm(x, g, 1e-5, dtype=F64)):
+        for y64 in (ref.layer_norm(x, g, b, 1e-5, dtype=F64), ref.layer_norm(x, g, None, 1e-5, dtype=F64),
+                    ref.rms_norm(x, g, 1e-5, dtype=F64)):
             floor("norm", block_rel_err(bf16_round(y64), y64, (1, None)), (rows, D))
         word, ids, pos, add = ko.embed_inputs(rows, D)
         y64 = ko.embed_ln64(word, ids, pos, add, g, b)
@@ -141,6 +147,11 @@ def test_ideal_norms_and_rope():
         for silu in (False, True):
             y64 = ref.group_norm(x, G, g, b, 1e-5, silu, dtype=F64)
             floor("group_norm", block_rel_err(bf16_round(y64), y64, (1, 16, C // G)), (B, S, C, G, silu))
+    for c in ko.GN_GEOM_CASES:
+        x, g, b = ko.gn_case_inputs(c)
+        for silu in (False, True):
+            y64 = ref.group_norm(x, c.G, g, b, 1e-5, silu, dtype=F64)
+            floor("group_norm", block_rel_err(bf16_round(y64), y64, (1, 16, c.C // c.G)), (c.id, silu), "group_norm, geometry")
     for B, T, H, Hk, d, L, pos0 in ko.ROPE_CASES:
         qkv = ko.rnd(B, T, (H + 2 * Hk) * d, seed=T + d)
         for y64 in ko.rope64(qkv, pos0, H, Hk, d):
@@ -672,6 +683,170 @@ def test_ideal_kv8_writer():
             floor("kv8", e, C)
     digit = 10.0 ** math.floor(math.log10(2 * worst))
     assert BOUND["kv8"] == pytest.approx(math.ceil(2 * worst / digit) * digit, rel=1e-12), worst
+
+
+# ------------------------------------------------------------------------------ norm.hip by launch geometry
+GN_BLOCK = lambda c: (1, 16, c.C // c.G)      # noqa: E731
+
+
+def _gn_ref(c):
+    x, g, b = ko.gn_case_inputs(c)
+    return x, g, b, ref.group_norm(x, c.G, g, b, 1e-5, False, dtype=F64)
+
+
+def test_gn_geometry_cases_reach_their_branches():
+    """under the CPU transcript of group_norm_geometry every case reaches the branches it names,
+    every branch of GN_BRANCHES has a case, and the two iid cases reach none of the launch
+    branches (one chunk, one block, VPT = 1: what the table exists to change)"""
+    seen = set()
+    for c in ko.GN_GEOM_CASES:
+        got = ko.gn_branches(c.B, c.S, c.C, c.G, c.Ca, ko.gn_geometry_model(c.B, c.S, c.C))
+        assert set(c.reaches) <= got, (c.id, set(c.reaches) - got)
+        assert set(c.reaches) <= set(ko.GN_BRANCHES)
+        seen |= set(c.reaches)
+        assert c.C <= ko.GN_MAX_C and c.C % 8 == 0 and c.C % c.G == 0 and c.Ca % 8 == 0
+    assert seen == set(ko.GN_BRANCHES), set(ko.GN_BRANCHES) - seen
+    for B, S, C, G in ko.GN_CASES:
+        got = ko.gn_branches(B, S, C, G, 0, ko.gn_geometry_model(B, S, C))
+        assert got <= {"idle row lanes", "Cg straddles vectors", "partial last apply block", "last block of one row"}, got
+    # the shapes past the cap: a third vector per thread that launch_group_norm / launch_channel_stats
+    # have no instantiation for, and an LDS request over 64 KiB
+    two = ko.gn_geometry_model(1, 8, ko.GN_MAX_C + 8)["two_pass"]
+    assert two["VPT"] == 3 and 2 * two["T"] < (ko.GN_MAX_C + 8) // 8
+    assert 4 * (2 * two["R"] + 2) * (ko.GN_MAX_C + 8) > 65536 >= 4 * (2 * 1 + 2) * ko.GN_MAX_C
+    assert ko.gn_geometry_model(1, 8, ko.GN_MAX_C)["two_pass"]["VPT"] == 2
+
+
+def test_gn_data_recipe():
+    for B, G in ((2, 32), (3, 32), (256, 8), (2, 2)):
+        mu, sigma = ko.gn_moments(B, G)
+        assert bool((mu[:, 1:] * mu[:, :-1] < 0).all())
+        ratio = mu.abs() / sigma
+        assert 1 <= float(ratio.min()) and float(ratio.max()) <= 8
+        r = sigma[1:] / sigma[:-1]
+        assert bool((torch.maximum(r, 1 / r) >= math.sqrt(2)).all())
+    c = ko.GN_GEOM_CASES[0]
+    x = ko.gn_case_inputs(c)[0].to(F64).view(c.B, c.S, c.G, -1)
+    mu, sigma = ko.gn_moments(c.B, c.G)
+    assert float(((x.mean((1, 3)) - mu) / sigma).abs().max()) < 0.1 and float((x.std((1, 3)) / sigma - 1).abs().max()) < 0.1
+
+
+def test_group_norm_planted_bugs_fail_on_every_case():
+    """the model without a bug is the reference (half the bound to spare); each planted bug is
+    over the bound in the worst block of every case it applies to"""
+    applied = {k: 0 for k in ("neighbour", "image0", "chunk", "vector", "ca", "clamp")}
+    for c in ko.GN_GEOM_CASES:
+        x, g, b, y64 = _gn_ref(c)
+        geom = ko.gn_geometry_model(c.B, c.S, c.C)
+        got = ko.gn_branches(c.B, c.S, c.C, c.G, c.Ca, geom)
+        err = lambda **bug: block_rel_err(ko.group_norm_model(x, c.G, g, b, 1e-5, False, geom, **bug), y64, GN_BLOCK(c))  # noqa: E731
+        assert err() < 0.5 * BOUND["group_norm"], c.id
+        figures = {"neighbour": err(neighbour_stats=True)}
+        if c.B > 1:
+            figures["image0"] = err(image0_stats=True)
+        if ko._cdiv(c.S, geom["two_pass"]["rows_per_chunk"]) > 1:
+            figures["chunk"] = err(drop_last_chunk=True)
+        if (c.C // 8) % 2:
+            figures["vector"] = err(last_vector="raw")
+            assert err(last_vector="unwritten") == math.inf
+        if c.Ca:
+            figures["ca"] = err(stats_a_past_ca=c.Ca)
+        fed = geom["stats_fed"]
+        if "partial last apply block" in got and c.S - (fed["blocks"] - 1) * fed["rows_per_block"] > 1:
+            figures["clamp"] = err(clamped_row=True)
+        print(c.id, {k: f"{v:.2e}" for k, v in figures.items()})
+        for k, v in figures.items():
+            applied[k] += 1
+            assert v > BOUND["group_norm"], (c.id, k, v)
+    assert all(n >= 2 for n in applied.values()), applied
+
+
+def test_iid_data_lets_wrong_statistics_through():
+    """why the recipe changed.  At test_group_norm's own (2, 4096, 320) / 32 with its kind of data
+    (every group of every image the same mean and variance) the neighbouring group's statistics
+    and image 0's statistics for every image pass the whole-tensor 1e-2; with gn_moments' data
+    both are orders of magnitude over the bound in their worst block."""
+    B, S, C, G = 2, 4096, 320, 32
+    x, g, b = ko.gn_inputs(B, S, C)
+    y64 = ref.group_norm(x, G, g, b, 1e-5, False, dtype=F64)
+    c = ko.GnCase(B, S, C, G, 0, ())
+    x2, g2, b2, y2 = _gn_ref(c)
+    for bug in ({"neighbour_stats": True}, {"image0_stats": True}):
+        iid = ko.group_norm_model(x, G, g, b, 1e-5, False, **bug)
+        own = ko.group_norm_model(x2, G, g2, b2, 1e-5, False, **bug)
+        e_glob, e_blk, e_own = global_rel_err(iid, y64), block_rel_err(iid, y64, GN_BLOCK(c)), block_rel_err(own, y2, GN_BLOCK(c))
+        print(f"{bug}: iid data whole tensor {e_glob:.2e}, worst block {e_blk:.2e}; own moments worst block {e_own:.2e}")
+        assert e_glob < 1e-2 and e_own > 100 * BOUND["group_norm"]
+    assert block_rel_err(ko.group_norm_model(x2, G, g2, b2, 1e-5, False), y2, GN_BLOCK(c)) < 0.5 * BOUND["group_norm"]
+
+
+def test_channel_stats_bound_holds_for_the_kernels_chain_and_rejects_a_dropped_row():
+    """channel_stats_kernel's own fp32 chain on the CPU stays inside the per-channel bound on every
+    case; one row (the image's last) or the last chunk left out is orders of magnitude outside"""
+    worst = 0.0
+    for c in {(c.B, c.S, c.C): c for c in ko.GN_GEOM_CASES}.values():
+        x = ko.gn_case_inputs(c)[0]
+        two = ko.gn_geometry_model(c.B, c.S, c.C)["two_pass"]
+        ok = ko.channel_stats_excess(ops.stats_to_float(ko.channel_stats_model(x, two)), x, two)
+        row = ko.channel_stats_excess(ops.stats_to_float(ko.channel_stats_model(x, two, drop_row=c.S - 1)), x, two)
+        print(f"{c.id}: chain at {ok:.3f} of the bound, a dropped row at {row:.0f}")
+        worst = max(worst, ok)
+        assert ok <= 1.0 and row > 100, (c.id, ok, row)
+        if ko._cdiv(c.S, two["rows_per_chunk"]) > 1:
+            rows = (ko._cdiv(c.S, two["rows_per_chunk"]) - 1) * two["rows_per_chunk"]
+            short = ko.gn_sums64(x, rows)[..., :2]
+            assert ko.channel_stats_excess(short, x, two) > 100, c.id
+    print(f"channel_stats: the chain's worst statistic at {worst:.3f} of its bound")
+
+
+def test_row_norm_cases_instantiate_every_vpl_and_t():
+    geoms = {D: ko.ln_geometry_model(D) for D in ko.ROW_NORM_D}
+    assert {g["VPL"] for g in geoms.values()} == set(range(1, 9))
+    assert {g["T"] for g in geoms.values()} == {1, 2, 4, 8, 16, 32, 64}
+    assert {320, 384, 768, 1024, 1280, 2048} <= set(ko.ROW_NORM_D) and max(ko.ROW_NORM_D) == ko.LN_MAX_D
+    for D, g in geoms.items():
+        rows = [r for r, d in ko.ROW_NORM_CASES if d == D]
+        assert g["rows_per_block"] + 1 in rows and 1 in rows and g["T"] * g["VPL"] * 8 >= D
+    assert (257, 8) in ko.ROW_NORM_CASES
+    assert {(r, D) for r in (1, 5) for D in (8, 136, 4096)} <= set(ko.ROW_NORM_CASES)      # the cases before the table grew
+
+
+def test_row_stats_floor():
+    """the two-pass formula in fp32 against fp64 over the row cases: ROW_STATS_FLOOR is its worst
+    row, rounded up to one digit, and the kernel's bound four times that"""
+    worst = [0.0, 0.0]
+    for rows, D in ko.ROW_NORM_CASES:
+        x = ko.norm_inputs(rows, D)[0]
+        e = ko.row_stats_err(*ko.row_stats32(x), x)
+        worst = [max(w, v) for w, v in zip(worst, e)]
+    print(f"row_stats in fp32: mean {worst[0]:.2e} of a deviation, rstd {worst[1]:.2e} relative")
+    for w, f in zip(worst, ko.ROW_STATS_FLOOR):
+        assert w <= f <= 3 * w, (worst, ko.ROW_STATS_FLOOR)
+    assert ko.ROW_STATS_BOUND == tuple(4 * f for f in ko.ROW_STATS_FLOOR)
+    FLOOR["row_stats mean"] = ("row_stats mean", worst[0])
+    FLOOR["row_stats rstd"] = ("row_stats rstd", worst[1])
+
+
+def test_layer_norm_that_reduces_two_rows_together_fails():
+    n = 0
+    for rows, D in ko.ROW_NORM_CASES:
+        x, g, b = ko.norm_inputs(rows, D)
+        for beta, rms in ((b, False), (None, False), (None, True)):
+            y64 = ref.rms_norm(x, g, 1e-5, dtype=F64) if rms else ref.layer_norm(x, g, beta, 1e-5, dtype=F64)
+            assert block_rel_err(ko.layer_norm_model(x, g, beta, rms=rms), y64, (1, None)) < 0.5 * BOUND["norm"]
+            if rows > 1:
+                e = block_rel_err(ko.layer_norm_model(x, g, beta, rms=rms, pair_rows=True), y64, (1, None))
+                assert e > BOUND["norm"], (rows, D, rms, e)
+                n += 1
+        if rows > 1:        # row_stats: the pooled statistics of rows 0 and 1 for both
+            xd = x.to(F64)[:2].reshape(1, -1)
+            mean = xd.sum(-1) / D
+            ms = ((xd - mean) ** 2).sum(-1) / D
+            m, r = ko.row_stats64(x)
+            m[:2], r[:2] = mean, (ms + 1e-5).rsqrt()
+            e = ko.row_stats_err(m, r, x)
+            assert e[0] > 1e3 * ko.ROW_STATS_BOUND[0] and e[1] > 1e3 * ko.ROW_STATS_BOUND[1], (rows, D, e)
+    assert n >= 100
 
 
 def test_glue_instruments():
