@@ -29,8 +29,6 @@ const uint16_t* opt_bptr(const c10::optional<at::Tensor>& t) {
   return bptr(*t);
 }
 
-// plans split-K and allocates its fp32 partial slabs from the caching allocator (graph-pool
-// safe inside a capture), then launches on the current stream
 long long* opt_stats(const c10::optional<at::Tensor>& t, long long images, int N) {
   if (!t.has_value() || !t->defined()) return nullptr;
   CHECK_DEV(*t);
@@ -67,32 +65,29 @@ void gemm_set_raster(int64_t plain, int64_t gated) {
   g_raster[1].store((int)gated);
 }
 
+// every GEMM / conv call: gemm_route decides (gemm.hip), this runs what it decided.  The temporaries
+// come from the caching allocator (graph-pool safe inside a capture), every launch goes to the current stream
 void run_gemm(GemmArgs& p, const at::Tensor& like) {
   raster_from_env();
   p.raster = g_raster[(p.act == 4 || p.act == 6) ? 1 : 0].load(std::memory_order_relaxed);   // gated: GEGLU (4) / SwiGLU (6)
-  // output statistics are fused into the LDS-staged bf16 epilogue; shapes that take another
-  // path (fp32 out, GEMV rows, batched, gated) get a separate per-channel statistics pass over
-  // the output; split-K shapes accumulate them in the reduce pass
   TORCH_CHECK(p.stats == nullptr || (p.N % 8 == 0 && p.ldc == p.N),
               "gemm/conv2d stats: the output channel count must be a multiple of 8 (GroupNorm consumers)");
-  const GemmPlan plan = gemm_plan(p);
-  p.cfg = plan.cfg;
-  p.split = plan.split;
-  // fp8 K/V emission runs in the LDS-staged epilogue (V transposed through the tile in LDS);
-  // the split-K reduce would scatter V byte by byte
-  if (p.kv8 != nullptr) p.split = 1;
+  const GemmRoute route = gemm_route(p);
+  TORCH_CHECK(route.refuse == nullptr, route.refuse);
+  at::Tensor tmp, ws;
+  if (route.pre == kPreGnApply) {
+    tmp = at::empty({p.M, p.K}, like.options().dtype(at::kBFloat16));
+    launch_group_norm_cs(p.A, nullptr, p.gn_stats, p.K, nullptr, p.gn_gamma, p.gn_beta, bptr_mut(tmp), p.M / p.gn_hw,
+                         p.gn_hw, p.K, p.gn_groups, p.gn_eps, 0, cur_stream());
+  } else if (route.pre == kPreRowStats) {
+    tmp = at::empty({p.M, 2}, like.options().dtype(at::kFloat));
+    launch_row_stats(p.A, tmp.data_ptr<float>(), p.M, p.K, p.ln_eps, cur_stream());
+  }
+  if (tmp.defined()) gemm_apply_pre(p, route.pre, tmp.data_ptr());
   long long* post_stats = nullptr;
-  if (p.stats != nullptr && (p.out_f32 || p.M <= 8 || (p.batch != 1 && !p.parity) || p.act == 4 || p.act == 6)) {
-    TORCH_CHECK(p.N <= GN_MAX_C, "gemm stats: the separate statistics pass takes N <= ", GN_MAX_C);
-    post_stats = p.stats;
-    p.stats = nullptr;
-  }
-  if (p.split > 1) {
-    auto ws = at::empty({(long long)p.split * p.batch * p.M * p.N}, like.options().dtype(at::kFloat));
-    launch_gemm(p, ws.data_ptr<float>(), cur_stream());
-  } else {
-    launch_gemm(p, nullptr, cur_stream());
-  }
+  if (route.post_stats) std::swap(post_stats, p.stats);
+  if (route.ws_floats > 0) ws = at::empty({route.ws_floats}, like.options().dtype(at::kFloat));
+  launch_gemm(p, route, ws.defined() ? ws.data_ptr<float>() : nullptr, cur_stream());
   if (post_stats != nullptr)
     launch_channel_stats(reinterpret_cast<const uint16_t*>(p.C), post_stats, p.M / p.stats_hw, p.stats_hw, p.N,
                          cur_stream());
@@ -117,7 +112,7 @@ void gemm(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tens
   TORCH_CHECK(out.size(0) == p.M, "gemm: M mismatch");
   if (act == 4 || act == 6) {
     // (the GEMV that takes <= 8 rows owns whole columns: any N; the MFMA gated tiles pair 4 columns)
-    TORCH_CHECK(p.Nw == 2 * p.N && p.K % 8 == 0 && (p.N % 4 == 0 || (p.M >= 1 && p.M <= 8 && p.lda % 8 == 0)),
+    TORCH_CHECK(p.Nw == 2 * p.N && p.K % 8 == 0 && (p.N % 4 == 0 || gemv_ok(p)),
                 "geglu/swiglu: W must be [2N,K], K%8==0, N%4==0 (any N for <= 8 rows with lda%8==0)");
   } else {
     TORCH_CHECK(p.Nw == p.N, "gemm: N mismatch");
@@ -162,20 +157,7 @@ void gemm(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tens
     p.gn_groups = (int)gn_groups;
     p.gn_hw = (int)gn_hw;
     p.gn_eps = (float)gn_eps;
-    if (gemm_areg_ok(p)) {
-      run_gemm(p, out);                           // the planner maps gn_stats to the A-in-registers kernel
-      return;
-    }
-    TORCH_CHECK(x.is_contiguous() && p.K % 8 == 0 && p.K % gn_groups == 0, "gemm gn fallback: contiguous rows");
-    at::Tensor xn = at::empty_like(x);
-    launch_group_norm_cs(bptr(x), nullptr, p.gn_stats, p.K, nullptr, p.gn_gamma, p.gn_beta, bptr_mut(xn),
-                         p.M / gn_hw, gn_hw, p.K, (int)gn_groups, (float)gn_eps, 0, cur_stream());
-    p.gn_stats = nullptr; p.gn_gamma = nullptr; p.gn_beta = nullptr;
-    p.A = bptr(xn);
-    run_gemm(p, out);
-    return;
-  }
-  if (row_stats.has_value() && row_stats->defined()) {
+  } else if (row_stats.has_value() && row_stats->defined()) {
     // LayerNorm row statistics of this output for a folded consumer (the LDS-staged epilogue
     // accumulates them; the planner then never splits K)
     CHECK_DEV(*row_stats); CHECK_CONTIG(*row_stats);
@@ -186,7 +168,9 @@ void gemm(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tens
                 "gemm: row_stats needs the LDS-staged bf16 epilogue (no GroupNorm stats / kv8, N % 8 == 0, M > 8)");
     p.row_stats = reinterpret_cast<long long*>(row_stats->data_ptr<int64_t>());
   }
-  if (ln_rows_fx.has_value() && ln_rows_fx->defined()) {
+  if (p.gn_stats != nullptr) {
+    // (excludes the LayerNorm folds, checked above)
+  } else if (ln_rows_fx.has_value() && ln_rows_fx->defined()) {
     // folded LayerNorm on row statistics a producer epilogue accumulated (no statistics pass)
     TORCH_CHECK(ln_wsum.has_value() && ln_wsum->defined() && ln_eps > 0 && !(ln_rows.has_value() && ln_rows->defined()),
                 "gemm: ln_rows_fx needs ln_wsum and ln_eps, and excludes ln_rows");
@@ -197,10 +181,7 @@ void gemm(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tens
     p.ln_rows_fx = reinterpret_cast<const long long*>(ln_rows_fx->data_ptr<int64_t>());
     p.ln_wsum = ln_wsum->data_ptr<float>();
     p.ln_eps = (float)ln_eps;
-    run_gemm(p, out);
-    return;
-  }
-  if (ln_rows.has_value() && ln_rows->defined()) {
+  } else if (ln_rows.has_value() && ln_rows->defined()) {
     // folded LayerNorm: raw rows in, per-row (mean, rstd) + column sums of the folded weights
     TORCH_CHECK(ln_wsum.has_value() && ln_wsum->defined(), "gemm: ln_rows needs ln_wsum");
     CHECK_DEV(*ln_rows); CHECK_CONTIG(*ln_rows); CHECK_DEV(*ln_wsum); CHECK_CONTIG(*ln_wsum);
@@ -212,23 +193,12 @@ void gemm(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tens
     p.ln_wsum = ln_wsum->data_ptr<float>();
   } else if (ln_wsum.has_value() && ln_wsum->defined() && ln_eps > 0) {
     // folded LayerNorm with the row statistics computed where they are cheapest: inside the
-    // A-in-registers kernel when it takes the shape (K = 320 / 640), else a row-stats pass
+    // A-in-registers kernel when it takes the shape (K = 320 / 640), else a row-stats pass (gemm_route)
     CHECK_DEV(*ln_wsum); CHECK_CONTIG(*ln_wsum);
     TORCH_CHECK(ln_wsum->scalar_type() == at::kFloat && ln_wsum->numel() == p.Nw, "gemm: ln_wsum fp32 [Nw]");
     TORCH_CHECK(p.M > 8 && p.K % 8 == 0 && p.lda % 8 == 0 && !p.out_f32, "gemm: folded LayerNorm needs the MFMA path");
     p.ln_wsum = ln_wsum->data_ptr<float>();
     p.ln_eps = (float)ln_eps;
-    // CASSMANTLE_LN_INKERNEL=0 forces the row-statistics pass (A/B and debugging knob)
-    static const bool inkernel = [] { const char* e = getenv("CASSMANTLE_LN_INKERNEL"); return !(e && e[0] == '0'); }();
-    if (!inkernel || !gemm_areg_ok(p)) {
-      TORCH_CHECK(x.is_contiguous() && p.K <= 4096, "gemm: folded LayerNorm row statistics need contiguous rows");
-      at::Tensor rows = at::empty({p.M, 2}, x.options().dtype(at::kFloat));
-      launch_row_stats(bptr(x), rows.data_ptr<float>(), p.M, p.K, (float)ln_eps, cur_stream());
-      p.ln_rows = rows.data_ptr<float>();
-      p.ln_eps = 0.f;
-      run_gemm(p, out);
-      return;
-    }
   }
   run_gemm(p, out);
 }
@@ -1307,6 +1277,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("gemm_record_keys", [](bool on) { gemm_record_keys(on); });
   m.def("gemm_last_key", []() { return gemm_last_key(); });
   m.def("gemm_last_plan", []() { int c, sp; gemm_last_plan(&c, &sp); return std::vector<int64_t>{c, sp}; });
+  m.def("gemm_last_route", []() {
+    const GemmRoute r = gemm_last_route();
+    return py::make_tuple(gemm_kernel_name(r.kernel), gemm_amode_name(r.mode), r.cfg, r.split, gemm_pre_name(r.pre), r.post_stats);
+  }, "the route of the calling thread's last GEMM / conv: (kernel, mode, cfg that ran, split, pre-pass, post_stats)");
   m.def("gemm_rms", &gemm_rms, nogil());
   m.def("conv2d", &conv2d, nogil());
   m.def("conv2d_up2", &conv2d_up2, nogil());

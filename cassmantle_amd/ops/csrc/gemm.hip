@@ -158,9 +158,19 @@ void gemm_set_override(int cfg, int split) {
   g_force_split = split;
 }
 
-static GemmPlan gemm_plan_impl(const GemmArgs& p);
+// the folds only the A-in-registers kernel computes: LayerNorm with in-kernel row statistics, and
+// GroupNorm of the A rows (gemm_route turns the calls that kernel does not take into a pre-pass first)
+static bool areg_only(const GemmArgs& p) {
+  return (p.ln_wsum != nullptr && p.ln_rows == nullptr && p.ln_rows_fx == nullptr) || p.gn_stats != nullptr;
+}
+
+// the planner: the menu's answer (tuning table, forced config, cost model) under what the call's
+// epilogue admits
+static GemmPlan gemm_plan_menu(const GemmArgs& p);
 GemmPlan gemm_plan(const GemmArgs& p) {
-  GemmPlan r = gemm_plan_impl(p);
+  if (g_record_key) g_last_key = gemm_key(p);
+  // neither the table nor a forced config may pick anything else
+  GemmPlan r = areg_only(p) ? GemmPlan{kGemmAregTile, 1} : gemm_plan_menu(p);
   if (p.row_stats != nullptr) {
     // output row statistics exist only in the shared LDS-staged epilogue (tile_epilogue):
     // no split-K, not the A-in-registers kernel
@@ -171,7 +181,7 @@ GemmPlan gemm_plan(const GemmArgs& p) {
   return r;
 }
 
-static GemmPlan gemm_plan_impl(const GemmArgs& p) {
+static GemmPlan gemm_plan_menu(const GemmArgs& p) {
   GemmPlan best{0, 1};
   if (g_force_cfg.load(std::memory_order_acquire) == -2) {
     static const bool from_env = [] {
@@ -183,13 +193,6 @@ static GemmPlan gemm_plan_impl(const GemmArgs& p) {
     (void)from_env;
   }
   const int force_cfg = g_force_cfg.load(), force_split = g_force_split.load();
-  if (g_record_key) g_last_key = gemm_key(p);
-  // in-kernel LayerNorm statistics exist only in the A-in-registers kernel (the binding checked
-  // eligibility, so neither the table nor a forced config may pick anything else)
-  if (p.ln_wsum != nullptr && p.ln_rows == nullptr && p.ln_rows_fx == nullptr) return GemmPlan{kGemmAregTile, 1};
-  // GroupNorm folded into the A rows: only the A-in-registers kernel applies it (the binding
-  // checked eligibility)
-  if (p.gn_stats != nullptr) return GemmPlan{kGemmAregTile, 1};
   if (force_cfg < 0) {
     bool have = false;
     GemmPlan tp{0, 1};
@@ -258,43 +261,109 @@ static GemmPlan gemm_plan_impl(const GemmArgs& p) {
   return best;
 }
 
-int gemm_plan_split(const GemmArgs& p) { return gemm_plan(p).split; }
+// skinny M (decode tokens, time-embedding / pooled projections): the weight-streaming GEMV of lm.hip
+bool gemv_ok(const GemmArgs& p) {
+  if (p.conv || !gemv_rows(p.M) || p.M < 1 || p.chan_bias != nullptr) return false;
+  return p.K % 8 == 0 && p.lda % 8 == 0 && (p.ldw ? p.ldw : p.K) % 8 == 0;
+}
 
-void launch_gemm(const GemmArgs& p, float* ws, hipStream_t s) {
-  const bool mfma_ok = (p.K % 8 == 0) && (!p.conv || p.Cin % 8 == 0) &&
-                       (p.conv || p.lda % 8 == 0) && (p.ldw % 8 == 0);
-  // skinny M (decode tokens, time-embedding / pooled projections): a weight-streaming GEMV
-  if (launch_gemv(p, s)) return;
-  if (!mfma_ok) {
-    if (p.act == ACT_GEGLU || p.act == ACT_SWIGLU) return;  // host guarantees gated shapes are MFMA-able
-    long long total = (long long)p.M * p.N;
-    dim3 grid((unsigned)((total + 255) / 256), 1, p.batch);
-    if (p.conv)
-      hipLaunchKernelGGL(gemm_simt_kernel<1>, grid, dim3(256), 0, s, p);
-    else
-      hipLaunchKernelGGL(gemm_simt_kernel<0>, grid, dim3(256), 0, s, p);
-    return;
+void gemm_apply_pre(GemmArgs& p, GemmPre pre, const void* tmp) {
+  if (pre == kPreRowStats) { p.ln_rows = static_cast<const float*>(tmp); p.ln_eps = 0.f; }
+  if (pre == kPreGnApply) { p.A = static_cast<const uint16_t*>(tmp); p.gn_stats = nullptr; p.gn_gamma = p.gn_beta = nullptr; }
+}
+
+static thread_local GemmRoute g_last_route{kGemmTiled, kA_c0, 0, 1, kPreNone, false, 0, nullptr};
+GemmRoute gemm_last_route() { return g_last_route; }
+static_assert(GN_MAX_C == 4096, "gemm_route's refusal text names the bound");
+
+GemmRoute gemm_route(const GemmArgs& call) {
+  GemmArgs p = call;
+  GemmRoute r{kGemmTiled, kA_c0, -1, 1, kPreNone, false, 0, nullptr};
+  auto refuse = [&r](bool cond, const char* why) { if (cond && r.refuse == nullptr) r.refuse = why; };
+  const bool gated = is_gated(p.act), contig = p.lda == p.K || p.M == 1;
+  // the pass a fold needs first where the A-in-registers kernel does not take the call as it stands
+  // (CASSMANTLE_LN_INKERNEL=0 forces the row-statistics pass: A/B and debugging knob)
+  static const bool ln_inkernel = [] { const char* e = getenv("CASSMANTLE_LN_INKERNEL"); return !(e && e[0] == '0'); }();
+  if (p.gn_stats != nullptr) {
+    if (!gemm_areg_ok(p)) r.pre = kPreGnApply;
+    refuse(r.pre && !(contig && p.K % 8 == 0 && p.gn_groups > 0 && p.K % p.gn_groups == 0), "gemm gn fallback: contiguous rows");
+  } else if (areg_only(p) && p.ln_eps > 0.f) {
+    if (!ln_inkernel || !gemm_areg_ok(p)) r.pre = kPreRowStats;
+    refuse(r.pre && !(contig && p.K <= 4096), "gemm: folded LayerNorm row statistics need contiguous rows");
   }
-  const bool buf = buf_ok(p);
+  alignas(64) static const char fresh[64] = {};   // stands for the pass's output, a fresh allocation
+  gemm_apply_pre(p, r.pre, fresh);
+  const GemmPlan plan = gemm_plan(p);
+  p.cfg = plan.cfg;
+  // fp8 K/V emission runs in the LDS-staged epilogue (V transposed through the tile in LDS);
+  // the split-K reduce would scatter V byte by byte
+  p.split = p.kv8 != nullptr ? 1 : plan.split;
+  // the kernel, in the order of preference
+  const bool mfma_ok = (p.K % 8 == 0) && (!p.conv || p.Cin % 8 == 0) && (p.conv || p.lda % 8 == 0) && (p.ldw % 8 == 0);
   const GemmTile* t = gemm_tile(p.cfg);
   const GemmTileFamily fam = t != nullptr ? t->family : kTileStatic;
-  if (fam == kTileAreg && gemm_areg_ok(p)) {
-    launch_gemm_areg(p, s);
-    return;
-  }
-  if (fam == kTilePingPong && family_runs(fam, p)) {
-    if (!p.conv) gemm_pp_c0_launch(p, ws, s);
-    else gemm_pp_c2_launch(p, ws, s);
-    return;
-  }
-  if (!p.conv) {
-    if (buf) gemm_c0_buf_launch(p, ws, s);
-    else gemm_c0_launch(p, ws, s);
-  } else if (p.Cin % 64 == 0) {
-    if (p.upsample) gemm_c3_launch(p, ws, s);
-    else if (buf) gemm_c2_buf_launch(p, ws, s);
-    else gemm_c2_launch(p, ws, s);
+  if (gemv_ok(p)) {
+    r.kernel = kGemmGemv;
+  } else if (!mfma_ok) {
+    // one thread per output element and the plain epilogue: nothing else of the call is computed
+    r.kernel = kGemmSimt;
+    if (p.conv) r.mode = kA_c1;
+    refuse(gated, "gemm: a gated call takes <= 8 rows (GEMV) or K, the row strides and Cin in multiples of 8 (MFMA)");
+    refuse(p.row_stats || p.kv8 || p.ln_rows || p.ln_rows_fx || p.ln_wsum || p.gn_stats || p.A2,
+           "gemm: K, the row strides and Cin must be multiples of 8 for row_stats, kv8, folded norms and two-source A");
+  } else if (fam == kTileAreg && gemm_areg_ok(p)) {
+    r.kernel = kGemmAreg;
+    r.cfg = kGemmAregTile;
+  } else if (fam == kTilePingPong && family_runs(fam, p)) {
+    r.kernel = kGemmPingPong;
+    r.mode = p.conv ? kA_c2_buf : kA_c0_buf;
+    r.cfg = gemm_tile_that_runs(p.cfg, true, gated, false, true);
   } else {
-    gemm_c1_launch(p, ws, s);
+    const bool buf = buf_ok(p);
+    if (!p.conv) r.mode = buf ? kA_c0_buf : kA_c0;
+    else if (p.Cin % 64 != 0) r.mode = kA_c1;
+    else r.mode = p.upsample ? kA_c3 : buf ? kA_c2_buf : kA_c2;
+    // (a gated call runs the gated instantiations, which store bf16)
+    r.cfg = gemm_tile_that_runs(p.cfg, false, gated, !gated && p.out_f32, r.mode == kA_c0_buf || r.mode == kA_c2_buf);
+  }
+  // split-K is the tile kernels' (slabs [z][split], summed by their reduce pass)
+  if (r.kernel == kGemmTiled || r.kernel == kGemmPingPong) r.split = p.split;
+  if (r.split > 1) r.ws_floats = (long long)r.split * p.batch * p.M * p.N;
+  // output statistics are fused into the LDS-staged bf16 epilogue of the MFMA kernels (split-K:
+  // into the reduce pass), for one batch or the parity classes of one image set, above the GEMV's
+  // row counts; every other call gets a per-channel statistics pass over the output
+  const bool fuses_stats = r.kernel != kGemmGemv && r.kernel != kGemmSimt && !p.out_f32 && !gated &&
+                           (p.batch == 1 || p.parity) && !gemv_rows(p.M);
+  r.post_stats = p.stats != nullptr && !fuses_stats;
+  refuse(r.post_stats && p.N > GN_MAX_C, "gemm stats: the separate statistics pass takes N <= 4096");
+  g_last_route = r;
+  return r;
+}
+
+void launch_gemm(const GemmArgs& call, const GemmRoute& r, float* ws, hipStream_t s) {
+  GemmArgs p = call;
+  p.cfg = r.cfg;
+  p.split = r.split;
+  switch (r.kernel) {
+    case kGemmGemv: (void)launch_gemv(p, s); return;
+    case kGemmSimt: {
+      // shapes the MFMA path does not take (K % 8 != 0 linear layers: the 4 -> 4 post_quant_conv)
+      const long long total = (long long)p.M * p.N;
+      dim3 grid((unsigned)((total + 255) / 256), 1, p.batch);
+      if (p.conv) hipLaunchKernelGGL(gemm_simt_kernel<1>, grid, dim3(256), 0, s, p);
+      else hipLaunchKernelGGL(gemm_simt_kernel<0>, grid, dim3(256), 0, s, p);
+      return;
+    }
+    case kGemmAreg: launch_gemm_areg(p, s); return;
+    case kGemmPingPong: (r.mode == kA_c0_buf ? gemm_pp_c0_launch : gemm_pp_c2_launch)(p, ws, s); return;
+    case kGemmTiled:
+      switch (r.mode) {
+        case kA_c0: gemm_c0_launch(p, ws, s); return;
+        case kA_c0_buf: gemm_c0_buf_launch(p, ws, s); return;
+        case kA_c1: gemm_c1_launch(p, ws, s); return;
+        case kA_c2: gemm_c2_launch(p, ws, s); return;
+        case kA_c2_buf: gemm_c2_buf_launch(p, ws, s); return;
+        case kA_c3: gemm_c3_launch(p, ws, s); return;
+      }
   }
 }

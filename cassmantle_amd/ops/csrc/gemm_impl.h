@@ -1074,7 +1074,7 @@ void launch_t(const GemmArgs& p, float* ws, hipStream_t s) {
 template <int I, int CONV, bool GEGLU, bool OUTF32, bool BUF>
 bool launch_row(int cfg, const GemmArgs& p, float* ws, hipStream_t s) {
   constexpr GemmTile t = kGemmTiles[I];
-  if constexpr ((t.family == kTileStatic || (t.family == kTileDeep && BUF && !OUTF32)) && (!GEGLU || t.gated())) {
+  if constexpr (gemm_tile_built(t, false, GEGLU, OUTF32, BUF)) {
     if (t.id != cfg) return false;
     launch_t<t.BM, t.BN, GEGLU ? t.GWM : t.WM, GEGLU ? t.GWN : t.WN, CONV, GEGLU, OUTF32, t.stages, BUF, t.producers>(p, ws, s);
     return true;

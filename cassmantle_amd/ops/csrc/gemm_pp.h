@@ -564,7 +564,7 @@ void launch_pp(const GemmArgs& p, float* ws, hipStream_t s) {
 template <int I, int CONV, bool GEGLU>
 bool launch_pp_row(int cfg, const GemmArgs& p, float* ws, hipStream_t s) {
   constexpr GemmTile t = kGemmTiles[I];
-  if constexpr (t.family == kTilePingPong && (!GEGLU || t.gated())) {
+  if constexpr (gemm_tile_built(t, true, GEGLU, false, true)) {
     if (t.id != cfg) return false;
     launch_pp<t.BM, t.BN, GEGLU ? t.GWM : t.WM, GEGLU ? t.GWN : t.WN, CONV, GEGLU>(p, ws, s);
     return true;

@@ -87,6 +87,22 @@ constexpr int gemm_default_tile(GemmTileFamily f, bool gated) {
 }
 constexpr int kGemmAregTile = 15;
 
+// has row t an instantiation?  In the gemm_pp.h units (pingpong): the ping-pong rows; in the
+// gemm_impl.h units: the static rows in every A-operand mode, the deep rings in the buffer-resource
+// modes (buf) with bf16 out; a gated call takes the rows with a gated wave layout.  The launchers
+// instantiate by this predicate and the route (gemm.hip) names the tile that runs by it
+constexpr bool gemm_tile_built(const GemmTile& t, bool pingpong, bool gated, bool out_f32, bool buf) {
+  const bool here = pingpong ? t.family == kTilePingPong
+                             : t.family == kTileStatic || (t.family == kTileDeep && buf && !out_f32);
+  return here && (!gated || t.gated());
+}
+// the tile that runs when a call names cfg: cfg itself, or its units' default when they hold no such instantiation
+constexpr int gemm_tile_that_runs(int cfg, bool pingpong, bool gated, bool out_f32, bool buf) {
+  const GemmTile* t = gemm_tile(cfg);
+  return t != nullptr && gemm_tile_built(*t, pingpong, gated, out_f32, buf)
+             ? cfg : gemm_default_tile(pingpong ? kTilePingPong : kTileStatic, gated);
+}
+
 static_assert(gemm_tile(gemm_default_tile(kTileStatic, true))->gated() && gemm_tile(gemm_default_tile(kTilePingPong, true))->gated() &&
                   gemm_tile(gemm_default_tile(kTileDeep, true))->gated() && gemm_tile(gemm_default_tile(kTilePingPong, false)) != nullptr &&
                   gemm_tile(kGemmAregTile)->family == kTileAreg,

@@ -75,7 +75,6 @@ struct GemmArgs {
 #define GEMM_MAX_SPLIT 16
 struct GemmPlan { int cfg; int split; };
 GemmPlan gemm_plan(const GemmArgs& p);
-int gemm_plan_split(const GemmArgs& p);
 // force a tile config (-1: cost model) and split-K factor (0: cost model) for every later plan
 void gemm_set_override(int cfg, int split);
 // measured tuning table: shape key (gemm_key) -> plan; key recording for the autotuner
@@ -87,8 +86,33 @@ int gemm_tune_size();
 void gemm_record_keys(bool on);
 std::string gemm_last_key();
 void gemm_last_plan(int* cfg, int* split);
-// ws: fp32 workspace of split * M * N floats when split > 1 (else may be null)
-void launch_gemm(const GemmArgs& p, float* ws, hipStream_t s);
+// Which kernel a call ends up in, and the passes around it: decided in one place, gemm_route (pure
+// host code: no launch, no allocation; tests/golden/gemm_routes.txt).  The caller (bindings.cpp
+// run_gemm) refuses, runs the pre-pass, allocates ws_floats, launches, runs the post-pass.
+enum GemmKernel { kGemmGemv, kGemmSimt, kGemmAreg, kGemmPingPong, kGemmTiled };   // lm.hip, gemm.hip, gemm_areg.hip, gemm_pp.h, gemm_impl.h
+// the A-operand mode = the gemm_c*.hip unit (ping-pong: gemm_pp_c0 / _c2 as c0_buf / c2_buf; the
+// kernels without units: c1 for a SIMT conv, else c0)
+enum GemmAMode { kA_c0, kA_c0_buf, kA_c1, kA_c2, kA_c2_buf, kA_c3 };
+// kPreRowStats: launch_row_stats(A) -> rows fp32 [M][2] (the folded LayerNorm's statistics where the
+// kernel cannot compute them); kPreGnApply: launch_group_norm_cs(A) -> xn bf16 [M][K] (the GroupNorm
+// fold where the A-in-registers kernel does not take the call).  gemm_apply_pre rewrites the arguments
+enum GemmPre { kPreNone, kPreRowStats, kPreGnApply };
+struct GemmRoute {
+  GemmKernel kernel; GemmAMode mode;
+  int cfg, split;          // cfg: the tile that RUNS (the planner's, unless its units hold no such instantiation; -1: no tile)
+  GemmPre pre;
+  bool post_stats;         // the kernel does not fuse p.stats: launch_channel_stats over C afterwards, p.stats cleared
+  long long ws_floats;     // split-K slabs, 0 if none
+  const char* refuse;      // non-null: no kernel computes this call; the text of the error
+};
+GemmRoute gemm_route(const GemmArgs& p);
+void gemm_apply_pre(GemmArgs& p, GemmPre pre, const void* tmp);   // tmp: the pre-pass's output
+GemmRoute gemm_last_route();                                      // of the calling thread, as gemm_last_plan
+inline const char* gemm_kernel_name(GemmKernel k) { static const char* const n[] = {"gemv", "simt", "areg", "pingpong", "tiles"}; return n[k]; }
+inline const char* gemm_amode_name(GemmAMode m) { static const char* const n[] = {"c0", "c0_buf", "c1", "c2", "c2_buf", "c3"}; return n[m]; }
+inline const char* gemm_pre_name(GemmPre p) { static const char* const n[] = {"none", "row_stats", "gn_apply"}; return n[p]; }
+// launches route.kernel in route.mode with route.cfg / route.split; ws: route.ws_floats floats (else may be null)
+void launch_gemm(const GemmArgs& p, const GemmRoute& route, float* ws, hipStream_t s);
 
 struct AttnArgs {
   const uint16_t* q; const uint16_t* k; const uint16_t* v; uint16_t* o;
@@ -166,7 +190,9 @@ void launch_rms_norm(const uint16_t* x, const uint16_t* gamma, uint16_t* y, long
                      hipStream_t s);
 
 // decode path (lm.hip)
-bool launch_gemv(const GemmArgs& p, hipStream_t s);   // false -> shape not handled (M > 8, conv, ...)
+constexpr bool gemv_rows(int M) { return M <= 8; }    // skinny: the row counts the GEMV is instantiated for
+bool gemv_ok(const GemmArgs& p);                      // the calls the GEMV takes (gemm.hip, with the other routes)
+bool launch_gemv(const GemmArgs& p, hipStream_t s);   // false -> !gemv_ok(p)
 struct RopeArgs {
   const uint16_t* qkv; long long ld;   // [B*T][ld], heads [q | k | v] x d
   const int* pos0;                     // [B] first position of this chunk (null -> 0)

@@ -443,9 +443,7 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_attn_kernel(DecodeArgs a) 
 }  // namespace
 
 bool launch_gemv(const GemmArgs& p, hipStream_t s) {
-  const long long ldw = p.ldw ? p.ldw : p.K;
-  if (p.conv || p.M > 8 || p.M < 1 || p.chan_bias != nullptr) return false;
-  if (p.K % 8 != 0 || p.lda % 8 != 0 || ldw % 8 != 0) return false;
+  if (!gemv_ok(p)) return false;
   if (p.M <= 1) gemv_launch<1>(p, s);
   else if (p.M <= 2) gemv_launch<2>(p, s);
   else if (p.M <= 4) gemv_launch<4>(p, s);

@@ -59,6 +59,8 @@ int main() {
           int c, s;
           gemm_last_plan(&c, &s);
           if (c != g.cfg || s != g.split) __atomic_add_fetch(&bad, 1, __ATOMIC_RELAXED);
+          const GemmRoute r = gemm_route(sh[i]), l = gemm_last_route();   // the route's thread-local too
+          if (l.kernel != r.kernel || l.cfg != r.cfg || l.split != r.split) __atomic_add_fetch(&bad, 1, __ATOMIC_RELAXED);
         }
       (void)t;
     });

@@ -43,7 +43,8 @@ def run(a):
             ext().gemm_set_override(cfg, 1)
             ops.linear(x, w, None, act=act)
             ext().gemm_set_override(-1, 0)
-            order.append({"cfg": cfg, "call": label, "plan": list(ext().gemm_last_plan())})
+            order.append({"cfg": cfg, "call": label, "plan": list(ext().gemm_last_plan()),
+                          "route": list(ext().gemm_last_route())})
     torch.cuda.synchronize()
     json.dump(order, open(a.order, "w"))
 
